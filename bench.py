@@ -3,6 +3,7 @@
 records (BASELINE.json metric; config 2 = 2^20 records, single AS key, per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--keysel zero|ifid] [--n N] [--rotate R]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 One process per GPU.  `--gpus N` with N > 1 and no torch.distributed environment starts the
@@ -20,9 +21,29 @@ hfv_verify_batches call on the rank's stream (one launch per 64 batches: the AES
 written into LDS once, the batches' tiles dealt to the CUs as one contiguous range), the launch
 and its table fill inside the timed region; --mode service posts the K batches to the resident
 service (hfv_service_run_async: a persistent grid fed through a host descriptor ring) and
---mode launch times one hfv_verify_records launch per step (all three are always measured:
-`batches`, `service`, `per_launch`).  Rank 0 prints one JSON line.  Besides the contract
-fields it carries:
+--mode launch times one hfv_verify_records launch per step.  Rank 0 prints one JSON line.
+
+A plain run does what the headline figure needs and no more: it generates the resident
+batches, runs W warm-up steps through the headline path and two untimed rehearsals of the
+K-step region (at most 1024 steps each), times the K steps (the K-step region up to --svc-reps
+times, the median reported; not repeated once the regions have taken 2 s),
+checks every bitmap of the last region bit for bit against the generator truth and prints the
+contract fields (`ms_per_step` = the region's milliseconds / K).
+
+    python bench.py ... --dump-outputs DIR
+
+then writes what the last timed step returned to its caller: DIR/verdicts.npy, the step's
+verdict bitmap as one float32 0/1 per record (workload br / br-host: action, verdict,
+egress_ifindex per frame, and a fixed seeded sample of the rewritten frame slots with its row
+indices in frames_index); at most 64 MB, larger outputs as a fixed seeded sample with an index
+array.  The inputs come from fixed seeds, so the files of two runs with the same arguments are
+comparable element for element.
+
+    python bench.py ... --full
+
+measures everything else as well (all three paths are then measured: `batches`, `service`,
+`per_launch`), each leg still switched by its own option.  Besides the contract fields the
+--full line carries:
   roofline      -- the headline kernel's algorithmic bytes (64 B read + 1/8 B verdict per
                    record) / its duration from the dispatch's own start/stop events (the
                    launch's, or the service grid's lifetime, over all K batches), against the
@@ -314,6 +335,151 @@ def settle(args):
     previous leg's heat.  --settle-s 0 turns it off."""
     if args.settle_s > 0:
         time.sleep(args.settle_s)
+
+
+DUMP_CAP_BYTES = 64 * 10 ** 6   # --dump-outputs writes at most this much
+SEED_DUMP = 0x5C100D00          # the sample of a larger output: the same elements in every run
+
+
+def dump_sample(n, row_bytes, share):
+    """Sorted indices of the rows of an n-row output that --dump-outputs keeps when the whole
+    output (row_bytes per row once written) exceeds `share` of DUMP_CAP_BYTES; None: all rows."""
+    keep = int(DUMP_CAP_BYTES * share) // row_bytes
+    if n <= keep:
+        return None
+    return np.sort(np.random.default_rng(SEED_DUMP).choice(n, size=keep, replace=False))
+
+
+def dump_outputs(W, dirpath, arrays):
+    """--dump-outputs: {name: array} -> DIR/<name>.npy (ranks above 0: <name>_rankR.npy).  float32
+    holds every value exactly (bytes, verdict bits, interface indices); 64-bit counters and row
+    indices go out as float64."""
+    os.makedirs(dirpath, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype.itemsize == 8 else np.float32)
+        total += a.nbytes
+        assert total <= DUMP_CAP_BYTES, f"--dump-outputs: {total} bytes with {name}"
+        np.save(os.path.join(dirpath, name + (f"_rank{W.rank}" if W.rank else "") + ".npy"), a)
+
+
+def verdict_arrays(bits_t, n):
+    """What a caller of the verify paths receives for one batch, for --dump-outputs: the verdict
+    bitmap as one 0/1 value per record (a sample of the records, with their indices, if larger
+    than the cap)."""
+    words = bits_t.cpu().numpy().view(np.uint8)
+    v = np.unpackbits(words, bitorder="little")[:n]
+    idx = dump_sample(n, 4 + 8, 1.0)
+    if idx is None:
+        return {"verdicts": v}
+    return {"verdicts": v[idx], "verdicts_index": idx.astype(np.int64)}
+
+
+def frame_arrays(frames, act, ver, egr, n):
+    """The router paths' outputs for --dump-outputs: action, verdict and egress interface of every
+    frame (of a sample above 2^20 frames), and a sample of the rewritten 2 KiB slots."""
+    idx = dump_sample(n, 3 * 4 + 8, 0.375)
+    rows = dump_sample(n, BR_SLOT * 4 + 8, 0.5)
+    rows = np.arange(n) if rows is None else rows
+    out = {"action": act if idx is None else act[idx], "verdict": ver if idx is None else ver[idx],
+           "egress_ifindex": egr if idx is None else egr[idx],
+           "frames": frames(rows), "frames_index": rows.astype(np.int64)}
+    if idx is not None:
+        out["index"] = idx.astype(np.int64)
+    return out
+
+
+PLAIN_REGION_BUDGET_S = 2.0   # a plain run stops repeating its K-step region after this much timed work
+PLAIN_REHEARSALS = 2          # untimed passes through the region before the timed ones
+
+
+def measure_plain(hfv, W, ctx, mode, n, first, rotate, steps, warmup, stream, bitmap_cap=1024, reps=3):
+    """A plain run's measurement: the headline path alone (mode: batches, service or launch) over
+    the same resident batches, in timed regions set up exactly as measure_hf sets up that path's,
+    with none of the other paths, kernel timings or diagnostics.  `warmup` untimed steps through
+    the same path come first, then PLAIN_REHEARSALS untimed regions.  The K-step region of batches / service is repeated `reps` times and
+    the median region reported, as in measure_hf, but no further once the regions have taken
+    PLAIN_REGION_BUDGET_S (a region that long has no need of a median).  Every bitmap the last
+    region wrote is checked bit for bit against the generator truth.  Returns the region's
+    seconds (max over ranks), the per-rank list, all regions, and the last step's bitmap."""
+    torch = W.torch
+    R = rotate
+    batches = [torch.empty((n, 64), dtype=torch.uint8, device="cuda") for _ in range(R)]
+    for i, b in enumerate(batches):
+        ctx.gen_records(b, n, SEED_RECORDS, first_index=first + i * n, stream=stream)
+    nb = -(-max(R, min(steps, bitmap_cap)) // R) * R    # a multiple of R: bitmap k always holds batch k % R
+    bitmaps = [torch.zeros((n + 63) // 64, dtype=torch.int64, device="cuda") for _ in range(nb)]
+    truth = [torch.from_numpy(truth_bitmap(n, first + i * n)).cuda() for i in range(R)]
+
+    def items(k):
+        return [(batches[i % R], n, bitmaps[i % nb]) for i in range(k)]
+
+    def check():
+        torch.cuda.synchronize()
+        for k in range(min(steps, nb)):
+            assert torch.equal(bitmaps[k], truth[k % R]), f"bitmap {k} != the generator truth of batch {k % R}"
+
+    def region(run_once, after):
+        for b in bitmaps:
+            b.zero_()
+        W.sync()
+        r = W.timed(1, run_once)
+        if after:
+            after()
+        check()
+        return r
+
+    def regions(run_once, after=None, rehearse=None):
+        # the first two passes through a region's host code run 10-25 % long (a --full run has been
+        # through it in its other legs by the time it times the headline): two untimed rehearsals
+        # of the region (`rehearse`: a longer one's first steps, every bitmap once)
+        for _ in range(PLAIN_REHEARSALS):
+            region(rehearse or run_once, after)
+        rs, spent = [], 0.0
+        while len(rs) < max(1, reps) and (not rs or spent < PLAIN_REGION_BUDGET_S):
+            rs.append(region(run_once, after))
+            spent += rs[-1][0]       # the max over ranks: every rank stops after the same region
+        return rs
+
+    short = min(steps, nb)
+    if mode == "launch":
+        for k in range(warmup):
+            ctx.verify_records(batches[k % R], n, bitmaps[k % nb], stream=stream)
+        for b in bitmaps:
+            b.zero_()
+        W.sync()
+        step = [0]
+
+        def launch_step():
+            k = step[0]
+            ctx.verify_records(batches[k % R], n, bitmaps[k % nb], stream=stream)
+            step[0] = k + 1
+
+        runs = [W.timed(steps, launch_step)]
+        check()
+    elif mode == "batches":
+        if warmup > 0:
+            ctx.verify_batches(ctx.service_batches(items(warmup)), stream=stream)
+            W.sync()
+        runs = regions(ctx.verify_batches_fn(ctx.service_batches(items(steps)), stream=stream),
+                       rehearse=ctx.verify_batches_fn(ctx.service_batches(items(short)), stream=stream))
+    else:
+        if warmup > 0:
+            service_grid(ctx, batches, warmup, bitmaps, n)
+            W.sync()
+        posts = ctx.service_batches(items(steps))
+        run_posts = ctx.service_run_async_fn(posts)
+        run_async = os.environ.get("HFV_BENCH_ASYNC", "1") != "0"
+        ctx.service_set_timing(False)
+        short_posts = ctx.service_batches(items(short))
+        runs = regions(run_posts if run_async else (lambda: service_grid(ctx, batches, steps, bitmaps, n, posts)),
+                       after=ctx.service_stop if run_async else None,   # reaps the exited grid
+                       rehearse=ctx.service_run_async_fn(short_posts) if run_async else
+                       (lambda: service_grid(ctx, batches, short, bitmaps, n, short_posts)))
+        ctx.service_set_timing(True)
+    all_ms = [round(r[0] * 1e3, 4) for r in runs]
+    el, per_rank = sorted(runs, key=lambda r: r[0])[len(runs) // 2]
+    return {"el": el, "per_rank_s": per_rank, "all_ms": all_ms, "last_bitmap": bitmaps[(steps - 1) % nb]}
 
 
 LOOKUPS_PER_PKT = 145   # T-table lookups per packet (11 + 8 x 16 + 6), each addressed by one v_perm
@@ -757,7 +923,7 @@ def br_cpu_baseline(frames_host, lens, ifidx, cfg, budget_s):
                          f"(scalar restatement of br/src/bpf/xdp.c process_packet + verify), 1 thread"}
 
 
-def measure_br(hfv, W, n, steps, warmup, hf_check=True):
+def measure_br(hfv, W, n, steps, warmup, hf_check=True, full=True, dump=None):
     """Config 4 on this rank: K pristine copies of the 2 KiB-slot batch resident in HBM, one
     hfv_br_process launch per step.  Returns (result fields, host frames sample, ...)."""
     from scion_hfv import topology as TP
@@ -795,17 +961,21 @@ def measure_br(hfv, W, n, steps, warmup, hf_check=True):
     it = iter(copies)
     el, per_rank = W.timed(steps, lambda: ctx.br_process(next(it), BR_SLOT, d_len, d_if, n, act, ver, egr, stats,
                                                          stream=stream))
-    ks = []
-    for c in copies[: min(steps, 10)]:
-        c.copy_(master)
-        ks.append(ctx.br_process_timed(c, BR_SLOT, d_len, d_if, n, act, ver, egr, stats, stream=stream))
-    ks.sort()
-    k_mean = float(np.mean(ks))
-    achieved = alg * n / (k_mean * 1e-3) / 1e9
-    res = {"el": el, "per_rank_s": per_rank, "k_mean": k_mean, "k_med": ks[len(ks) // 2], "alg": alg,
-           "achieved": achieved, "n_good": n_good}
+    res = {"el": el, "per_rank_s": per_rank, "alg": alg, "n_good": n_good}
+    if dump:   # the last timed step's outputs: per-frame results and the frames it rewrote in place
+        last = copies[steps - 1]
+        dump_outputs(W, dump, frame_arrays(lambda rows: last[torch.from_numpy(rows).cuda()].cpu().numpy(),
+                                           act.cpu().numpy(), ver.cpu().numpy(), egr.cpu().numpy(), n))
+    if full:   # the kernel's own time (dispatch events), in launches of their own
+        ks = []
+        for c in copies[: min(steps, 10)]:
+            c.copy_(master)
+            ks.append(ctx.br_process_timed(c, BR_SLOT, d_len, d_if, n, act, ver, egr, stats, stream=stream))
+        ks.sort()
+        k_mean = float(np.mean(ks))
+        res.update({"k_mean": k_mean, "k_med": ks[len(ks) // 2], "achieved": alg * n / (k_mean * 1e-3) / 1e9})
     sample = None
-    if W.rank == 0:
+    if W.rank == 0 and full:   # for the CPU baseline
         m = min(n, 1 << 16)
         sample = (master[:m].cpu().numpy(), lens[:m], np.array(ifis, dtype=np.uint32)[tid[:m]], cfg,
                   act[:m].cpu().numpy())
@@ -819,7 +989,8 @@ def run_br(args, W):
     if steps > 32:
         raise SystemExit("--workload br keeps one pristine 2 KiB-slot batch per timed step in HBM: use --steps <= 32")
     import scion_hfv as hfv
-    r, sample = measure_br(hfv, W, n, steps, args.warmup, hf_check=not args.no_hf_check)
+    r, sample = measure_br(hfv, W, n, steps, args.warmup, hf_check=not args.no_hf_check, full=args.full,
+                           dump=args.dump_outputs)
     result = {
         "metric": "Mpkt/s full border-router per-packet path (parse + hop-field MAC verify + rewrite), "
                   "mixed 64-1500 B frames",
@@ -832,14 +1003,16 @@ def run_br(args, W):
         "config": {"workload": f"config 4: {n} frames per GPU through hfv_br_process as br1-ff00_0_1-1"
                                + ("" if not args.no_hf_check else ", HF check off (ENABLE_HF_CHECK=OFF)"),
                    "frames_per_gpu": n, "slot_bytes": BR_SLOT, "parallelism": f"batch-sharded x{W.size}, no collective"},
-        "roofline": {"bound": "hbm", "achieved": round(r["achieved"], 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(r["achieved"] / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(f"br:{n}"),
-                     "kernel": "k_br_process", "kernel_ms_mean": round(r["k_mean"], 5),
-                     "kernel_ms_median": round(r["k_med"], 5), "algorithmic_bytes_per_frame": round(r["alg"], 2),
-                     "kernel_mpkts": round(n / r["k_mean"] / 1e3, 1)},
         "per_rank_ms": [round(x * 1e3, 4) for x in r["per_rank_s"]],
     }
-    if W.rank == 0 and W.size == 1 and args.cpu_budget > 0 and sample is not None:
+    if args.full:
+        result["roofline"] = {"bound": "hbm", "achieved": round(r["achieved"], 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(r["achieved"] / HBM_PEAK_GBS, 4), "traffic": pmc_traffic(f"br:{n}"),
+                              "kernel": "k_br_process", "kernel_ms_mean": round(r["k_mean"], 5),
+                              "kernel_ms_median": round(r["k_med"], 5),
+                              "algorithmic_bytes_per_frame": round(r["alg"], 2),
+                              "kernel_mpkts": round(n / r["k_mean"] / 1e3, 1)}
+    if args.full and W.rank == 0 and W.size == 1 and args.cpu_budget > 0 and sample is not None:
         hf, lens, ifx, cfg, act = sample
         a_cpu, result["cpu_baseline"] = br_cpu_baseline(hf, lens, ifx, cfg, min(args.cpu_budget, 5.0))
         result["cpu_baseline"]["actions_match_gpu"] = bool((a_cpu == act).all()) if not args.no_hf_check else None
@@ -878,6 +1051,8 @@ def run_br_host(args, W):
         total += max(W.gather(time.perf_counter() - t0))
     if not args.no_register:
         ctx.host_unregister(frames)
+    if args.dump_outputs:
+        dump_outputs(W, args.dump_outputs, frame_arrays(lambda rows: frames[rows], act, ver, egr, n))
     path = ("DMA of %d-byte header windows (unregistered ring)" % (args.window or 256) if args.no_register else
             "zero-copy: registered ring, the kernel reads 128-byte header windows and writes back rewritten rows")
     result = {
@@ -1075,20 +1250,72 @@ def run_hf(args, W):
     ctx = make_ctx(hfv, W.device, keysel)
     stream = torch.cuda.current_stream().cuda_stream
     cus = torch.cuda.get_device_properties(W.device).multi_processor_count
-    tb = apply_thread_budget(args, thread_budget(W, ctx))
+    headline = "launch" if args.launch_only else args.mode
     svc_blocks = 0
     if args.same_device and W.size > 1:
         # ranks sharing one GPU: each service grid takes its share of the CUs (one block per CU
         # holds the CU's LDS), so the grids run side by side instead of one after the other
         svc_blocks = max(1, cus // W.size)
         ctx.service_set_grid(svc_blocks)
+
+    def line(elapsed):
+        """The contract fields of the result line, for `elapsed` seconds over the K timed steps."""
+        return {
+            "metric": METRIC,
+            "value": round(total * args.steps / elapsed / 1e6, 2),
+            "unit": "Mpkt/s",
+            "n_gpus": W.n_gpus, "ranks": W.size,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 5),
+            "higher_is_better": True,
+            "scaling": "strong" if args.strong else "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "data": "synthetic (64 B SCION records, splitmix64 seed 0x5C100001, 1/16 corrupted MACs; generated on device)",
+            "config": {"workload": f"config {'3' if keysel else '2'}: "
+                                   f"{f'{total} x 64 B records per step in total' if args.strong else f'{n} x 64 B records per GPU per step'}, "
+                                   f"{'256 ingress-interface keys (KEYSEL_IFID)' if keysel else 'single AS key'}",
+                       "records_per_gpu": n, "record_bytes": 64, "keysel": args.keysel,
+                       "resident_batches_per_gpu": args.rotate,
+                       "resident_bytes_per_gpu": args.rotate * n * 64,
+                       "parallelism": f"batch-sharded x{W.size}, no collective"},
+            "path": {"service": "resident service: one persistent grid; the K batches and a stop descriptor posted "
+                                "through the host descriptor ring by one hfv_service_run_async call, which launches the "
+                                "grid after them; the timed region's closing device synchronize waits for the grid to "
+                                "exit; posting, grid launch, table fill and drain inside the timed region",
+                     "batches": "stream-ordered batch list: the K batches in one hfv_verify_batches call on the rank's "
+                                "stream (one launch per 64 batches: table fill, ramp and tail paid once per launch); the "
+                                "timed region's closing device synchronize waits for it",
+                     "launch": "one hfv_verify_records launch per batch"}[headline],
+        }
+
+    if not args.full:   # a plain run: the headline path alone
+        p = measure_plain(hfv, W, ctx, headline, n, first, args.rotate, args.steps, args.warmup, stream,
+                          reps=args.svc_reps)
+        result = line(p["el"])
+        result["timed_regions_ms"] = p["all_ms"]
+        result["per_rank_ms"] = {"min": round(min(p["per_rank_s"]) * 1e3, 4), "max": round(max(p["per_rank_s"]) * 1e3, 4),
+                                 "all": [round(x * 1e3, 4) for x in p["per_rank_s"]]}
+        if args.same_device:
+            result["same_device"] = {"ranks": W.size, "physical_gpus": 1, "service_grid_blocks": svc_blocks,
+                                     "note": "launcher rehearsal: every rank on GPU 0"}
+        if args.dump_outputs:
+            dump_outputs(W, args.dump_outputs, verdict_arrays(p["last_bitmap"], n))
+        if W.rank == 0:
+            print(json.dumps(result), flush=True)
+        ctx.close()
+        return
+
+    tb = apply_thread_budget(args, thread_budget(W, ctx))
     m = measure_hf(hfv, W, ctx, args.keysel, n, first, args.rotate, args.steps, args.warmup, stream, reps=args.svc_reps,
                    service=not args.launch_only)
+    if args.dump_outputs:   # every path left its verdicts in these bitmaps, each checked against the truth
+        dump_outputs(W, args.dump_outputs, verdict_arrays(m["bitmaps"][(args.steps - 1) % len(m["bitmaps"])], n))
     # every rank's median event-timed grid (the service's kernel time per rank), and no rank starts
     # an extra leg (host threads, PCIe copies) while another is still in its headline regions
     per_rank_grid = W.gather(m["grid_ms"] or 0.0)
     W.barrier()
-    headline = "launch" if args.launch_only else args.mode
     elapsed = {"service": m["svc_el"], "launch": m["launch_el"], "batches": m["bat_el"]}[headline]
     if headline == "batches":
         m["per_rank_s"] = m["bat_per_rank_s"]
@@ -1115,26 +1342,8 @@ def run_hf(args, W):
         kern = {"kernel": "k_verify_batches (one batch per launch: hfv_verify_records)", "kernel_ms_mean": round(m["k_mean"], 5),
                 "kernel_ms_median": round(m["k_med"], 5), "algorithmic_bytes_per_launch": int(bytes_per_batch)}
         traffic = pmc_traffic(f"{args.keysel}:{n}:rot{args.rotate}")
-    result = {
-        "metric": METRIC,
-        "value": round(total * args.steps / elapsed / 1e6, 2),
-        "unit": "Mpkt/s",
-        "n_gpus": W.n_gpus, "ranks": W.size,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 5),
-        "higher_is_better": True,
-        "scaling": "strong" if args.strong else "weak",
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (64 B SCION records, splitmix64 seed 0x5C100001, 1/16 corrupted MACs; generated on device)",
-        "config": {"workload": f"config {'3' if keysel else '2'}: "
-                               f"{f'{total} x 64 B records per step in total' if args.strong else f'{n} x 64 B records per GPU per step'}, "
-                               f"{'256 ingress-interface keys (KEYSEL_IFID)' if keysel else 'single AS key'}",
-                   "records_per_gpu": n, "record_bytes": 64, "keysel": args.keysel,
-                   "resident_batches_per_gpu": args.rotate,
-                   "resident_bytes_per_gpu": args.rotate * n * 64,
-                   "parallelism": f"batch-sharded x{W.size}, no collective"},
+    result = line(elapsed)
+    result.update({
         "roofline": dict({"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic}, **kern,
                          achievable_peak=m["stream_read"]["gbs"],
@@ -1147,14 +1356,6 @@ def run_hf(args, W):
         "stream_read": m["stream_read"],
         "ceilings": ceilings(args.keysel, n, m["bat_mhz"] if headline == "batches" else m["mhz"], cus,
                              "batches" if headline == "batches" else "service"),
-        "path": {"service": "resident service: one persistent grid; the K batches and a stop descriptor posted "
-                            "through the host descriptor ring by one hfv_service_run_async call, which launches the "
-                            "grid after them; the timed region's closing device synchronize waits for the grid to "
-                            "exit; posting, grid launch, table fill and drain inside the timed region",
-                 "batches": "stream-ordered batch list: the K batches in one hfv_verify_batches call on the rank's "
-                            "stream (one launch per 64 batches: table fill, ramp and tail paid once per launch); the "
-                            "timed region's closing device synchronize waits for it",
-                 "launch": "one hfv_verify_records launch per batch"}[headline],
         "batches": {"mpkts": round(total * args.steps / m["bat_el"] / 1e6, 2),
                     "ms_per_step": round(m["bat_el"] / args.steps * 1e3, 5),
                     "kernel_ms": round(m["bat_kernel_ms"], 4),
@@ -1181,7 +1382,7 @@ def run_hf(args, W):
                         "all": [round(x * 1e3, 4) for x in m["per_rank_s"]],
                         "grid_ms": [round(x, 4) for x in per_rank_grid] if headline == "service" else None},
         "host_threads": tb,
-    }
+    })
     if args.same_device:
         result["same_device"] = {"ranks": W.size, "physical_gpus": 1,
                                  "service_grid_blocks": svc_blocks,
@@ -1357,7 +1558,14 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="every rank on GPU 0 (launcher rehearsal on 1 GPU; gloo; service grids of cus/ranks blocks)")
     ap.add_argument("--dry-run", action="store_true", help="launcher check: gloo ranks, no GPU work")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the other paths, kernel timings and roofline, configs 3/4/5, the "
+                         "host legs and the CPU baseline (each still switched by its own option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB)")
     args = ap.parse_args()
+    if args.dump_outputs and (args.dry_run or args.workload == "loop"):
+        ap.error("--dump-outputs: this workload returns no arrays (use it with --workload hf, br or br-host)")
     if args.steps is None:
         args.steps = {"hf": 200, "br": 10, "br-host": 5, "loop": 1}[args.workload]
     if args.warmup is None:

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 R=$1; shift
 for r in $(seq 1 $R); do
   for lib in "$@"; do
-    out=$(HFV_LIB=$lib timeout -k 10 150 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-budget 0 --no-host-e2e 2>/dev/null | grep '^{') || { echo "$r $(basename $lib) FAILED"; exit 1; }
+    out=$(HFV_LIB=$lib timeout -k 10 150 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-budget 0 --no-host-e2e 2>/dev/null | grep '^{') || { echo "$r $(basename $lib) FAILED"; exit 1; }
     echo "$out" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); c=d['config3']

@@ -19,7 +19,7 @@ def main():
         i = args.index("--")
         args, extra = args[:i], args[i + 1:]
     rounds, libs = int(args[0]), args[1:]
-    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-extras", "--cpu-budget", "0", "--no-host-e2e"] + \
+    bench = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-extras", "--cpu-budget", "0", "--no-host-e2e"] + \
         (extra or ["--steps", "20", "--warmup", "5"])
     for r in range(rounds):
         for spec in libs:

@@ -26,16 +26,16 @@ for s in "$@"; do
         run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q -p no:cacheprovider --timeout 300 --timeout-method thread
         rc=$?; [[ $rc -gt 1 ]] && exit $rc ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit $? ;;
-    bench) run bench 600 python bench.py --steps 20 --warmup 5 || exit $? ;;
-    bench_quick) run bench_quick 300 python bench.py --steps 20 --warmup 5 --no-extras --cpu-budget 0 --no-host-e2e || exit $? ;;
+    bench) run bench 600 python bench.py --full --steps 20 --warmup 5 || exit $? ;;
+    bench_quick) run bench_quick 300 python bench.py --full --steps 20 --warmup 5 --no-extras --cpu-budget 0 --no-host-e2e || exit $? ;;
     prof)
         run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-            python3 bench.py --steps 20 --warmup 5 || exit $?
+            python3 bench.py --full --steps 20 --warmup 5 || exit $?
         python3 scripts/prof_summary.py "$OUT"/prof/run_kernel_trace.csv "$OUT"/prof/verify_by_batch.json > /dev/null ;;
     pmc_zero) run pmc_zero 1100 bash scripts/pmc_round.sh zero svc rot8 || exit $? ;;
     pmc_ifid) run pmc_ifid 1100 bash scripts/pmc_round.sh ifid svc rot8 || exit $? ;;
     pmc_br) run pmc_br 1100 bash scripts/pmc_round.sh br || exit $? ;;
-    br) run bench_br 600 python bench.py --workload br || exit $? ;;
+    br) run bench_br 600 python bench.py --full --workload br || exit $? ;;
     brhost) run bench_brhost 600 python bench.py --workload br-host || exit $? ;;
     loop) run bench_loop 300 python bench.py --workload loop || exit $? ;;
     looptest) run pytest_loop 300 python -u -m pytest tests/test_gpu_loop.py -m gpu -x -v -p no:cacheprovider --timeout 120 --timeout-method thread || exit $? ;;

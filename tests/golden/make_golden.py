@@ -15,6 +15,9 @@ Sources of truth, in order:
     bitmaps are computed by the REFERENCE aes.c (oracle/_ref/libaesref.so: aes_cmac soft
     path and aes_cmac_unaligned128 AES-NI path), cross-checked with OpenSSL's CMAC and
     with our restatement (oracle/libhfvoracle.so).  Any disagreement aborts.
+  * ref_random.npz: the REFERENCE aes.c's verify bitmaps and CMAC tags on the random inputs of
+    tests/orc.random_cases(), so that tests/test_oracle.py's random comparison also runs where
+    the reference build is absent.
 """
 import ctypes
 import json
@@ -214,7 +217,28 @@ def make_hf(n, keysel, raw_keys):
                 valid=valid, seed=np.uint64(SEED_RECORDS), keysel=np.int32(keysel), nkeys=np.int32(nkeys))
 
 
+def make_ref_random():
+    """ref_random.npz: what the reference build computes on tests/orc.random_cases() -- the
+    verify bitmaps of the random records for both key rules (soft and AES-NI path must agree)
+    and aes_cmac / aes_cmac_no_loops of every random message."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import orc
+    recs, key, datas = orc.random_cases()
+    raw = orc.gen_key_table(256)
+    hk, valid = orc.key_table(raw)
+    bits = []
+    for keysel in (0, 1):
+        soft, hw = (orc.ref_verify_records(recs, raw, hk, valid, keysel, aesni=a) for a in (0, 1))
+        assert np.array_equal(soft, hw)
+        bits.append(soft)
+    macs = np.array([[np.frombuffer(ref_cmac(d, key, fn), dtype=np.uint8) for fn in ("aes_cmac", "aes_cmac_no_loops")]
+                     for d in datas])
+    np.savez_compressed(os.path.join(HERE, "ref_random.npz"), pass_bits=np.array(bits), macs=macs)
+    print(f"ref_random.npz: {len(recs)} random records x 2 key rules, {len(datas)} CMAC lengths x 2 functions")
+
+
 def main():
+    make_ref_random()
     kat = make_kat()
     with open(os.path.join(HERE, "kat.json"), "w") as f:
         json.dump(kat, f, indent=1)

@@ -24,6 +24,8 @@ NLM_F_REQUEST, NLM_F_ACK, NLM_F_EXCL, NLM_F_CREATE = 1, 4, 0x200, 0x400
 NLMSG_ERROR = 2
 IFLA_ADDRESS, IFLA_IFNAME, IFLA_MTU, IFLA_LINKINFO = 1, 3, 4, 18
 IFLA_INFO_KIND, IFLA_INFO_DATA = 1, 2
+IFLA_AF_SPEC = 26
+IFLA_INET6_ADDR_GEN_MODE, IN6_ADDR_GEN_MODE_NONE = 8, 1
 VETH_INFO_PEER = 1
 IFF_UP = 1
 
@@ -95,16 +97,24 @@ def set_mac(name, mac):
     _request(RTM_NEWLINK, 0, _ifinfo(socket.if_nametoindex(name)) + _attr(IFLA_ADDRESS, bytes.fromhex(mac.replace(":", ""))))
 
 
+def no_ipv6_address(name):
+    """ip link set dev name addrgenmode none: the link gets no IPv6 link-local address when it
+    comes up, so the kernel sends no duplicate-address, router-solicitation or listener-report
+    frames on it."""
+    mode = _attr(IFLA_INET6_ADDR_GEN_MODE, struct.pack("=B", IN6_ADDR_GEN_MODE_NONE))
+    af_spec = _attr(IFLA_AF_SPEC, _attr(socket.AF_INET6, mode))
+    _request(RTM_NEWLINK, 0, _ifinfo(socket.if_nametoindex(name)) + af_spec)
+
+
 def evaluation_links():
     """veth_setup.bash: veth0-veth1 and veth2-veth3 with the MACs 02:00:00:00:00:0N, up.
-    Returns {name: ifindex}.  IPv6 is switched off on them first, so the kernel's own neighbour
-    discovery frames do not join the test traffic."""
+    Returns {name: ifindex}.  The links get no IPv6 address (a request on the link itself, inside
+    this namespace), so the kernel's own neighbour discovery frames do not join the test traffic."""
     for a, b in (("veth0", "veth1"), ("veth2", "veth3")):
         veth_pair(a, b)
     for k in range(4):
         try:
-            with open("/proc/sys/net/ipv6/conf/veth%d/disable_ipv6" % k, "w") as f:
-                f.write("1")
+            no_ipv6_address("veth%d" % k)
         except OSError:
             pass
     for k in range(4):

@@ -166,3 +166,17 @@ def br_process(frames, lens, ifidx, cfg, key0_hop_key=None, stats=None, hf_check
 
 def load_golden(name):
     return dict(np.load(os.path.join(GOLDEN, name)))
+
+
+RANDOM_CMAC_LENS = list(range(0, 70)) + [127, 128, 129, 255]
+
+
+def random_cases(seed=7):
+    """The inputs of the random comparison with the reference build (tests/test_oracle.py; their
+    reference results are recorded in tests/golden/ref_random.npz by make_golden.py): 5000 records
+    of random bytes in every field, garbage headers and flags included, a random CMAC key and one
+    random message per length of RANDOM_CMAC_LENS.  Returns (records, key, messages)."""
+    rng = np.random.default_rng(seed)
+    recs = rng.integers(0, 256, size=(5000, 64), dtype=np.uint8)
+    key = rng.integers(0, 256, 16, dtype=np.uint8).tobytes()
+    return recs, key, [rng.integers(0, 256, L, dtype=np.uint8).tobytes() for L in RANDOM_CMAC_LENS]

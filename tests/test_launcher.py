@@ -41,7 +41,7 @@ def test_two_product_ranks_on_one_gpu():
     """Two ranks, each verifying its own resident records with the HIP kernels (launch path),
     every bitmap checked against the generator truth inside bench.py.  The line reports the
     one physical GPU and the two ranks separately."""
-    d = _bench("--gpus", "2", "--same-device", "--launch-only", "--n", "65536", "--rotate", "2", "--steps", "4",
+    d = _bench("--full", "--gpus", "2", "--same-device", "--launch-only", "--n", "65536", "--rotate", "2", "--steps", "4",
                "--warmup", "2", "--no-extras", "--no-host-e2e", "--cpu-budget", "0", timeout=600)
     assert d["n_gpus"] == 1 and d["ranks"] == 2 and d["same_device"]["ranks"] == 2
     assert len(d["per_rank_ms"]["all"]) == 2
@@ -53,7 +53,7 @@ def test_two_batch_list_ranks_on_one_gpu():
     """The default headline (one hfv_verify_batches launch per K steps) with two ranks on GPU 0:
     each rank's launches use the whole chip and share it with the other's; every bitmap is
     checked against the generator truth inside bench.py; the line reports both ranks."""
-    d = _bench("--gpus", "2", "--same-device", "--n", "262144", "--rotate", "2", "--steps", "8", "--warmup", "2",
+    d = _bench("--full", "--gpus", "2", "--same-device", "--n", "262144", "--rotate", "2", "--steps", "8", "--warmup", "2",
                "--no-extras", "--no-host-e2e", "--cpu-budget", "0", timeout=600)
     assert d["n_gpus"] == 1 and d["ranks"] == 2 and len(d["per_rank_ms"]["all"]) == 2
     assert d["roofline"]["kernel"] == "k_verify_batches" and d["value"] > 0
@@ -65,7 +65,7 @@ def test_two_service_ranks_on_one_gpu():
     """the service path with two ranks on GPU 0, each resident grid limited to
     half the CUs (hfv_service_set_grid: CUs / ranks), both timed together; every bitmap is checked
     against the generator truth inside bench.py, and each rank reports its thread budget."""
-    d = _bench("--gpus", "2", "--same-device", "--n", "262144", "--rotate", "2", "--steps", "8", "--warmup", "2",
+    d = _bench("--full", "--gpus", "2", "--same-device", "--n", "262144", "--rotate", "2", "--steps", "8", "--warmup", "2",
                "--no-extras", "--no-host-e2e", "--cpu-budget", "0.2", "--mode", "service", timeout=600)
     assert d["n_gpus"] == 1 and d["ranks"] == 2 and len(d["per_rank_ms"]["all"]) == 2
     # VERDICT r04 #6: the N > 1 line carries its CPU baseline (rank 0, after every rank's GPU legs)
@@ -97,7 +97,7 @@ def test_two_loop_ranks_on_one_gpu():
     from scion_hfv import evaluation as E
     from test_gpu_loop import _oracle
     total = 300_000
-    d = _bench("--gpus", "2", "--same-device", "--n", "65536", "--rotate", "2", "--steps", "4", "--warmup", "2",
+    d = _bench("--full", "--gpus", "2", "--same-device", "--n", "65536", "--rotate", "2", "--steps", "4", "--warmup", "2",
                "--no-host-e2e", "--cpu-budget", "0", "--big-n", "0", "--br-n", "0", "--loop-n", str(total),
                "--loop-chunk", "16384", "--loop-chunks", "6", "--loop-threads", "3", "--loop-consumers", "2",
                "--loop-digest", timeout=900)
@@ -123,7 +123,7 @@ def test_single_rank_line_keeps_the_contract():
     """The driver's N = 1 line: every contract key, `value` = whole-job Mpkt/s over the timed
     steps, the roofline and cpu_baseline objects (bench contract, task 4), and the per-grid
     clock and balance-weight diagnostics of the service regions."""
-    d = _bench("--steps", "6", "--warmup", "2", "--no-extras", "--no-host-e2e", "--loop-n", "0", "--cpu-budget", "1",
+    d = _bench("--full", "--steps", "6", "--warmup", "2", "--no-extras", "--no-host-e2e", "--loop-n", "0", "--cpu-budget", "1",
                timeout=600)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
@@ -138,3 +138,47 @@ def test_single_rank_line_keeps_the_contract():
     assert c["value"] > 0 and c["cores"] >= 1 and c["kind"] in ("reference", "port") and c["sample"]
     s = d["service"]
     assert len(s["grids_mhz"]) == len(s["grids_ms"]) and all(len(w) == 9 for w in s["weights"])
+
+
+PLAIN_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config")
+FULL_ONLY = ("roofline", "cpu_baseline", "service", "batches", "per_launch", "stream_read", "ceilings", "config3",
+             "config4", "config5_loop", "host_e2e", "pcie_probe", "sustained", "per_call", "mall_resident",
+             "hbm_resident")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["batches", "service", "launch"])
+def test_plain_run_times_the_headline_alone_and_dumps_its_last_step(mode, tmp_path):
+    """A plain run (no --full): the contract fields with `value` = Mpkt/s over the K timed steps of
+    the chosen path, none of the --full legs in the line, and --dump-outputs holding the last timed
+    step's verdicts (step K - 1 verifies resident batch (K - 1) % R): one float32 0/1 per record,
+    equal to the generator truth of that batch, ragged last word included."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    n, R, K = 65536 + 37, 3, 8
+    d = _bench("--steps", str(K), "--warmup", "2", "--n", str(n), "--rotate", str(R), "--mode", mode,
+               "--dump-outputs", str(tmp_path / "out"))
+    for k in PLAIN_KEYS:
+        assert k in d, k
+    assert not [k for k in FULL_ONLY if k in d]
+    assert d["n_gpus"] == 1 and d["steps"] == K and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["unit"] == "Mpkt/s" and d["dtype"] == "u8" and d["metric"] == bench.METRIC
+    assert d["value"] > 0 and abs(d["value"] - n / (d["ms_per_step"] * 1e-3) / 1e6) / d["value"] < 0.01
+    assert os.listdir(tmp_path / "out") == ["verdicts.npy"]
+    v = np.load(tmp_path / "out" / "verdicts.npy")
+    assert v.dtype == np.float32 and v.shape == (n,)
+    assert np.array_equal(v != 0, ~bench.corrupted(n, ((K - 1) % R) * n))
+    assert set(np.unique(v)) <= {0.0, 1.0}
+
+
+def test_dump_sample_is_fixed_and_within_the_cap():
+    """--dump-outputs keeps a larger output as a sample: the same sorted, distinct rows in every
+    run, and no more than the cap allows; an output under the cap is kept whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.dump_sample(1 << 20, 12, 1.0) is None
+    a, b = bench.dump_sample(1 << 24, 12, 1.0), bench.dump_sample(1 << 24, 12, 1.0)
+    assert (a == b).all() and (a[1:] > a[:-1]).all() and 0 <= a[0] and a[-1] < 1 << 24
+    assert len(a) * 12 <= bench.DUMP_CAP_BYTES < (len(a) + 1) * 12
