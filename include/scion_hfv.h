@@ -154,7 +154,7 @@ struct hfv_batch {
  * launch; more are split): the round tables are written into LDS once for all of them, and
  * the batches' tiles are dealt to the CUs as one contiguous range.  Records written by earlier
  * work on `stream` are read, the bitmaps are complete for later work on it -- the fast path
- * for callers whose batches come from a copy or a parse kernel on a stream (one
+ * for callers whose batches come from a copy or from hfv_extract_records on a stream (one
  * hfv_verify_records launch per batch pays the table fill and the grid's ramp and tail per
  * batch).  Each batch is checked as hfv_verify_records checks one; empty batches are skipped. */
 int hfv_verify_batches(hfv_ctx *ctx, const struct hfv_batch *batches, size_t count, void *stream);
@@ -162,6 +162,46 @@ int hfv_verify_batches(hfv_ctx *ctx, const struct hfv_batch *batches, size_t cou
  * dispatch end of the last) in *kernel_ms.  For benchmarks. */
 int hfv_verify_batches_timed(hfv_ctx *ctx, const struct hfv_batch *batches, size_t count, void *stream,
                              float *kernel_ms);
+
+/* ---- frames -> records -> verdict bits --------------------------------------------------
+ * The producer in front of the record verify: parse_underlay + parse_scion + parse_scion_path
+ * (br/src/bpf/parser.h:45-204) over raw Ethernet frames, and nothing else of process_packet (no
+ * lookup, no rewrite, no counters).  Per frame a status: 0, or the verdict the router
+ * (hfv_br_process) records when its parse fails at the same place.  The router's build options
+ * (HFV_BR_NO_*) do not apply: IPv4, IPv6 and the standard SCION path type are always parsed. */
+#define HFV_FRAME_OK 0
+#define HFV_FRAME_PARSE_ERROR 17      /* a bound check of parse_scion / parse_scion_path failed */
+#define HFV_FRAME_NOT_SCION 26        /* whatever parse_underlay rejects */
+#define HFV_FRAME_NOT_IMPLEMENTED 34  /* SCION version != 0, or path type != 1 */
+/* The compact record: InfoField at 0, HopField at 8, 4 bytes of padding.  Recommended with
+ * hfv_ctx_set_record_layout(ctx, 0, 8): a wave's 64 records are 1536 contiguous bytes. */
+#define HFV_FRAME_REC_STRIDE 24
+/* Parse one frame on the host; *inf_off / *hf_off (the byte offsets of the current InfoField and
+ * HopField) are valid when the result is HFV_FRAME_OK.  Returns the status (>= 0), or -EINVAL for
+ * NULL arguments.  The scalar counterpart of the extract kernel, for control-plane checks. */
+int hfv_frame_locate(const uint8_t *frame, size_t len, uint32_t *inf_off, uint32_t *hf_off);
+/* Frame i at frames + i*slot (slot % 8 == 0, >= 64), len[i] its length (clamped to slot).  For
+ * every frame: status[i], and into record i (recs + i*stride; recs and stride 8-byte aligned,
+ * stride >= inf_off + 8 and >= hf_off + 12 of the ctx's record layout) the frame's current
+ * InfoField (8 B at inf_off) and HopField (12 B at hf_off), both all zeros where status[i] != 0.
+ * Record bytes outside the two fields are unspecified afterwards.  frames is never written, no
+ * byte at or past frames + n*slot is read, and bytes of a slot at or past len[i] count as absent.
+ * All pointers are device pointers; stream-ordered like hfv_verify_records; needs no key table.
+ * Like every data-path call it first stops a running verify service (whose grid holds the LDS
+ * the kernel needs).  n == 0 returns 0. */
+int hfv_extract_records(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
+                        void *recs, size_t stride, uint8_t *status, void *stream);
+/* Same, then waits and stores the kernel's execution time (dispatch start/stop) in *kernel_ms. */
+int hfv_extract_records_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
+                              void *recs, size_t stride, uint8_t *status, void *stream, float *kernel_ms);
+/* Frames to verdict bits in one call: hfv_extract_records, hfv_verify_batches over recs (one batch;
+ * the ctx's key table, keysel and record layout), then pass_bits &= (status == 0), all on `stream`
+ * with no host synchronisation.  Bit i is 1 iff status[i] == 0 and the record verifies; bits >= n
+ * of the last word are 0.  recs and status are the caller's scratch and outputs (the library
+ * allocates nothing on this path). */
+int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
+                      void *recs, size_t stride, uint8_t *status, uint64_t *pass_bits, void *stream);
+
 /* Verdict counts for the verify-only paths, modelled on record_verdict (xdp.c:54-70) but NOT
  * its layout: counters[slot][0] += packets that verified, counters[slot][1] += packets dropped
  * as VERDICT_INVALID_HF, where slot is the packet's AS-ingress interface (IFID & 0xff,

@@ -818,6 +818,90 @@ int hfv_verify_batches_timed(hfv_ctx *ctx, const struct hfv_batch *batches, size
     return 0;
 }
 
+// ---- frames -> records -> verdict bits ---------------------------------------------------
+
+static int frames_check(const hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
+                        const void *recs, size_t stride, const uint8_t *status)
+{
+    if (!frames || !len || !recs || !status) return fail(-EINVAL, "null buffer");
+    if ((slot & 7) || slot < 64) return fail(-EINVAL, "slot %zu: must be a multiple of 8, at least 64", slot);
+    if (slot > (1u << 24)) return fail(-EINVAL, "slot %zu > 16 MiB", slot);
+    if (((uintptr_t)recs & 7) || (stride & 7)) return fail(-EINVAL, "records and stride must be 8-byte aligned");
+    if (stride < (size_t)ctx->inf_off + 8 || stride < (size_t)ctx->hf_off + 12)
+        return fail(-EINVAL, "stride %zu too small for INF@%u/HF@%u", stride, ctx->inf_off, ctx->hf_off);
+    if (stride > (1u << 24)) return fail(-EINVAL, "stride %zu > 16 MiB", stride);
+    if (n > ((size_t)1 << 36)) return fail(-EINVAL, "%zu frames (at most 2^36)", n);
+    return 0;
+}
+
+// The extract kernel needs LDS on every CU it runs on, which a running service grid holds until
+// it stops: like every other data-path call, these stop the service after its posted batches.
+int hfv_extract_records(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, void *recs,
+                        size_t stride, uint8_t *status, void *stream)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    int rc = frames_check(ctx, frames, slot, len, n, recs, stride, status);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    int e = launch_extract_records(frames, slot, len, n, (uint8_t *)recs, stride, ctx->inf_off, ctx->hf_off, status,
+                                   pick_stream(ctx, stream));
+    return e == hipSuccess ? 0 : hip_fail((hipError_t)e, "extract_records launch");
+}
+
+int hfv_extract_records_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
+                              void *recs, size_t stride, uint8_t *status, void *stream, float *kernel_ms)
+{
+    if (!ctx || !kernel_ms) return fail(-EINVAL, "null argument");
+    *kernel_ms = 0.0f;
+    if (n == 0) return 0;
+    int rc = frames_check(ctx, frames, slot, len, n, recs, stride, status);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    for (int i = 0; i < 2; ++i)
+        if (!ctx->tev[i]) HIP_TRY(hipEventCreate(&ctx->tev[i]));
+    int e = launch_extract_records(frames, slot, len, n, (uint8_t *)recs, stride, ctx->inf_off, ctx->hf_off, status,
+                                   pick_stream(ctx, stream), ctx->tev[0], ctx->tev[1]);
+    if (e != hipSuccess) return hip_fail((hipError_t)e, "extract_records launch");
+    HIP_TRY(hipEventSynchronize(ctx->tev[1]));
+    HIP_TRY(hipEventElapsedTime(kernel_ms, ctx->tev[0], ctx->tev[1]));
+    return 0;
+}
+
+int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, void *recs,
+                      size_t stride, uint8_t *status, uint64_t *pass_bits, void *stream)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    int rc = frames_check(ctx, frames, slot, len, n, recs, stride, status);
+    if (rc) return rc;
+    const struct hfv_batch b = {recs, stride, n, pass_bits};
+    rc = batches_check(ctx, &b, 1);   // the bitmap's pointer and alignment
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    hipStream_t st = pick_stream(ctx, stream);
+    int e = launch_extract_records(frames, slot, len, n, (uint8_t *)recs, stride, ctx->inf_off, ctx->hf_off, status,
+                                   st);
+    if (e != hipSuccess) return hip_fail((hipError_t)e, "extract_records launch");
+    rc = batches_launch(ctx, &b, 1, st, nullptr, nullptr);
+    if (rc) return rc;
+    e = launch_mask_status(status, n, pass_bits, st);
+    return e == hipSuccess ? 0 : hip_fail((hipError_t)e, "status mask launch");
+}
+
+// Diagnostic (not part of include/scion_hfv.h): the last step of hfv_verify_frames alone,
+// pass_bits[i / 64] &= (status[i] == 0), so that scripts/frames_probe.py can time the mask kernel.
+extern "C" int hfv_debug_mask_status(hfv_ctx *ctx, const uint8_t *status, size_t n, uint64_t *pass_bits, void *stream)
+{
+    if (!ctx || !status || !pass_bits || n == 0 || ((uintptr_t)pass_bits & 7)) return fail(-EINVAL, "bad argument");
+    DeviceGuard g(ctx->device);
+    int e = launch_mask_status(status, n, pass_bits, pick_stream(ctx, stream));
+    return e == hipSuccess ? 0 : hip_fail((hipError_t)e, "status mask launch");
+}
+
 // Diagnostic (not part of include/scion_hfv.h): block 0's shader clock (s_memtime) and 100 MHz
 // s_memrealtime at the start and at the end of the last hfv_verify_batches launch (out[0..3]);
 // with words >= 4 + 2 * 1024 also every block's s_memrealtime at its entry (out[4 + k]) and when it

@@ -303,6 +303,15 @@ int launch_br_process(const LaunchGeom &g, const DevState *st, uint8_t *pkts, si
                       uint8_t *action, uint8_t *verdict, int32_t *egress_ifindex, uint64_t *stats, void *stream,
                       void *ev_start = nullptr, void *ev_stop = nullptr, uint8_t *out = nullptr);
 
+// frames -> records (hfv_frames_kernel.hip).  The staged kernel (16-byte loads of each frame's
+// first 128 bytes into LDS) runs where slot >= 128, slot % 16 == 0 and frames is 16-byte aligned,
+// the direct one (every field read from global memory) otherwise.
+int launch_extract_records(const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, uint8_t *recs,
+                           size_t stride, uint32_t inf_off, uint32_t hf_off, uint8_t *status, void *stream,
+                           void *ev_start = nullptr, void *ev_stop = nullptr);
+// pass_bits[i / 64] &= ballot(status[i] == 0), the last step of hfv_verify_frames
+int launch_mask_status(const uint8_t *status, size_t n, uint64_t *bits, void *stream);
+
 // pinned key map (hfv_keymap.cpp)
 int keymap_open_ro(const char *path, const void **mapping);
 int keymap_create(const char *path, uint32_t mode);   // empty map (header only) if the file does not exist

@@ -34,6 +34,12 @@ REC_SIZE = 64
 SVC_RING = 128   # resident-service descriptor ring (kSvcRing, csrc/hfv_internal.h)
 SVC_INLINE = 64  # descriptors a service grid gets in its kernel arguments (kSvcInline)
 BYTES_PER_PACKET = 64 + 1.0 / 8  # algorithmic HBM bytes per verified record
+# frame parser statuses (hfv_frame_locate, hfv_extract_records): 0 or the router's parse verdict
+FRAME_OK = 0
+FRAME_PARSE_ERROR = 17
+FRAME_NOT_SCION = 26
+FRAME_NOT_IMPLEMENTED = 34
+FRAME_REC_STRIDE = 24  # compact record: set_record_layout(0, 8), InfoField | HopField | 4 B pad
 
 
 class HfvError(RuntimeError):
@@ -74,6 +80,10 @@ def lib():
         "hfv_verify_records_timed": (i32, [vp, vp, sz, sz, vp, vp, ctypes.POINTER(ctypes.c_float)]),
         "hfv_verify_batches": (i32, [vp, vp, sz, vp]),
         "hfv_verify_batches_timed": (i32, [vp, vp, sz, vp, ctypes.POINTER(ctypes.c_float)]),
+        "hfv_frame_locate": (i32, [vp, sz, ctypes.POINTER(u32), ctypes.POINTER(u32)]),
+        "hfv_extract_records": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp]),
+        "hfv_extract_records_timed": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_float)]),
+        "hfv_verify_frames": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
         "hfv_ctx_describe": (i32, [vp, ctypes.c_char_p, sz]),
         "hfv_ctx_attach_keymap": (i32, [vp, ctypes.c_char_p]),
         "hfv_keymap_path": (i32, [ctypes.c_char_p, ctypes.c_char_p, sz]),
@@ -215,6 +225,17 @@ def decode_key_b64(s: str) -> bytes:
     out = ctypes.create_string_buffer(16)
     _check(lib().hfv_decode_key_b64(s.encode(), out))
     return out.raw
+
+
+def frame_locate(frame_bytes):
+    """hfv_frame_locate: (status, inf_off, hf_off) of one Ethernet frame, parsed on the host as
+    the extract kernel parses it; the offsets are valid for status FRAME_OK."""
+    buf = bytes(frame_bytes)
+    inf, hf = ctypes.c_uint32(), ctypes.c_uint32()
+    rc = lib().hfv_frame_locate(buf, len(buf), ctypes.byref(inf), ctypes.byref(hf))
+    if rc < 0:
+        _check(rc)
+    return rc, inf.value, hf.value
 
 
 def verify_macinput(macinput: bytes, expected: int, hop_key_bytes) -> bool:
@@ -456,6 +477,33 @@ class Ctx:
         ms = ctypes.c_float(0.0)
         _check(lib().hfv_verify_batches_timed(self._h, arr, len(arr), _stream(stream), ctypes.byref(ms)))
         return ms.value
+
+    def extract_records(self, frames, slot, lens, n, recs, status, stride=FRAME_REC_STRIDE, stream=None):
+        """hfv_extract_records: frames (n slots of `slot` bytes, lens u16) -> records with the
+        ctx's record layout and a parse status per frame (FRAME_*).  Device buffers."""
+        _check(lib().hfv_extract_records(self._h, _ptr(frames), slot, _ptr(lens), n, _ptr(recs), stride,
+                                         _ptr(status), _stream(stream)))
+
+    def extract_records_timed(self, frames, slot, lens, n, recs, status, stride=FRAME_REC_STRIDE, stream=None):
+        """extract_records, waited for; returns the kernel's execution time in ms."""
+        ms = ctypes.c_float(0.0)
+        _check(lib().hfv_extract_records_timed(self._h, _ptr(frames), slot, _ptr(lens), n, _ptr(recs), stride,
+                                               _ptr(status), _stream(stream), ctypes.byref(ms)))
+        return ms.value
+
+    def verify_frames(self, frames, slot, lens, n, recs, status, pass_bits, stride=FRAME_REC_STRIDE, stream=None):
+        """hfv_verify_frames: extract, verify and mask on one stream; bit i of pass_bits is 1 iff
+        frame i parsed (status 0) and its current hop field verifies."""
+        _check(lib().hfv_verify_frames(self._h, _ptr(frames), slot, _ptr(lens), n, _ptr(recs), stride, _ptr(status),
+                                       _ptr(pass_bits), _stream(stream)))
+
+    def mask_status(self, status, n, pass_bits, stream=None):
+        """Diagnostic (hfv_debug_mask_status): verify_frames' last step alone,
+        pass_bits[i / 64] &= (status[i] == 0)."""
+        L = lib()
+        L.hfv_debug_mask_status.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_void_p]
+        _check(L.hfv_debug_mask_status(self._h, _ptr(status), n, _ptr(pass_bits), _stream(stream)))
 
     def verdict_counters(self, recs, n, pass_bits, counters, stride=REC_SIZE, stream=None):
         """record_verdict for the verify-only paths: counters (device u64[256][2]) +=

@@ -1,0 +1,195 @@
+#!/usr/bin/env python3
+"""Frames -> verdict bits against the router on the same frames, one run, one ctx.
+
+Builds bench.py's config-4 batch (2^20 frames in 2 KiB slots: 2 GiB, past the Infinity Cache) and
+a dense 144-byte-slot ring of the same frames, and after a warm-up takes medians of --reps runs of
+  hfv_extract_records_timed, hfv_verify_batches_timed over the 24-byte records, the whole
+  hfv_verify_frames region (torch events), the region without the mask kernel (extract +
+  verify_batches, torch events), the mask kernel alone (hfv_debug_mask_status, torch events), and
+  hfv_br_process_timed on the same frames,
+plus a streaming read of the frame buffer (hfv_debug_stream_read, as bench.py uses) and the
+extract kernel's algorithmic bytes: per frame the 64-byte lines that hold the fields the parser
+reads, + 24 written + 3 of len/status.  Prints one JSON object and writes it to --out.
+
+  timeout -k 10 300 python scripts/frames_probe.py [--direct] [--extract-only] [--slots 2048,144]
+
+--direct places the frame buffer 8 bytes off a 16-byte boundary, which the staged kernel's 16-byte
+loads cannot take: the library then runs the direct kernel (every field read from global memory),
+the alternative of the A/B in profiles/ab_index.md.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "scion-xdp-br_amd"))
+
+import numpy as np  # noqa: E402
+
+
+def field_lines(frame, base):
+    """Number of 64-byte lines that hold the bytes the parser and the copy read of `frame`
+    placed at byte address `base`."""
+    import scion_hfv as hfv
+    st, inf, hf = hfv.frame_locate(frame)
+    assert st == 0
+    ip = 14
+    v4 = frame[12:14] == b"\x08\x00"
+    sc = ip + (4 * (frame[ip] & 0x0F) if v4 else 40) + 8
+    haddr = frame[sc + 9]
+    meta = sc + 28 + 8 + 4 * ((haddr >> 2) & 2) + 4 * ((haddr >> 6) & 2)
+    spans = [(12, 2), (ip, 1), (ip + (9 if v4 else 6), 1), (sc, 1), (sc + 8, 2), (meta, 4), (inf, 8), (hf, 12)]
+    lines = set()
+    for off, size in spans:
+        lines.update(range((base + off) // 64, (base + off + size - 1) // 64 + 1))
+    return len(lines)
+
+
+def med(xs):
+    return float(statistics.median(xs))
+
+
+def region_ms(torch, fn, reps):
+    out = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1 << 20)
+    ap.add_argument("--reps", type=int, default=11)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--slots", default="2048,144")
+    ap.add_argument("--direct", action="store_true", help="misalign the frame buffer: the direct kernel")
+    ap.add_argument("--extract-only", action="store_true", help="A/B runs: the extract kernel alone")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frames", "frames_probe.json"))
+    args = ap.parse_args()
+    args.extract_only |= args.direct   # the other legs want the aligned buffer
+    import torch
+    import bench
+    import scion_hfv as hfv
+    from scion_hfv import topology as TP
+
+    n, reps = args.n, max(10, args.reps)
+    frames, ifis, _, _ = bench.br_templates()
+    tmpl, tid, lens, ifx, n_good = bench.br_batch(n, 0)
+    ctx = hfv.Ctx(0)
+    ctx.key_add(0, TP.KEYS[1])
+    ctx.br_set_config(TP.br_config("br1"))
+    ctx.set_record_layout(0, 8)
+    stride = hfv.FRAME_REC_STRIDE
+    d_tid = torch.from_numpy(tid.astype(np.int64)).cuda()
+    d_if = torch.from_numpy(ifx.view(np.int32)).cuda()
+    recs = torch.zeros((n, stride), dtype=torch.uint8, device="cuda")
+    status = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    bits = torch.zeros((n + 63) // 64, dtype=torch.int64, device="cuda")
+    act = torch.zeros(n, dtype=torch.uint8, device="cuda")
+    ver = torch.zeros_like(act)
+    egr = torch.zeros(n, dtype=torch.int32, device="cuda")
+    result = {"n": n, "reps": reps, "kernel": "direct" if args.direct else "staged", "hbm_peak_GBs": bench.HBM_PEAK_GBS,
+              "device": torch.cuda.get_device_name(0), "slots": {}}
+    for slot in [int(s) for s in args.slots.split(",")]:
+        assert 64 <= slot <= bench.BR_SLOT and slot % 8 == 0
+        buf = torch.empty(n * slot + 16, dtype=torch.uint8, device="cuda")
+        off = (-buf.data_ptr()) % 16 + (8 if args.direct else 0)
+        master = buf[off:off + n * slot].view(n, slot)
+        torch.index_select(torch.from_numpy(np.ascontiguousarray(tmpl[:, :slot])).cuda(), 0, d_tid, out=master)
+        assert master.data_ptr() % 16 == (8 if args.direct else 0)
+        d_len = torch.from_numpy(np.minimum(lens, slot).astype(np.uint16).view(np.int16)).cuda()
+        # algorithmic bytes: per template and placement phase (the ring's frames start at i * slot)
+        phases = 64 // np.gcd(slot, 64)
+        lines = np.array([[field_lines(f, p * slot) for p in range(phases)] for f in frames])
+        alg = float((lines[tid, np.arange(n) % phases] * 64).mean()) + stride + 3
+        r = {"slot": slot, "frame_bytes": int(master.numel()), "algorithmic_bytes_per_frame": round(alg, 2)}
+
+        def extract():
+            return ctx.extract_records_timed(master, slot, d_len, n, recs, status)
+
+        for _ in range(args.warmup):
+            extract()
+        ex = [extract() for _ in range(reps)]
+        r["status_nonzero"] = int((status != 0).sum())   # 0: every benched frame parses
+        r["extract_ms"] = round(med(ex), 5)
+        r["extract_ms_min_max"] = [round(min(ex), 5), round(max(ex), 5)]
+        r["extract_GBs"] = round(alg * n / (med(ex) * 1e-3) / 1e9, 1)
+        r["extract_frac_of_peak"] = round(r["extract_GBs"] / bench.HBM_PEAK_GBS, 4)
+        r["extract_Gpkts"] = round(n / (med(ex) * 1e-3) / 1e9, 2)
+        if not args.extract_only:
+            sr = [ctx.stream_read_ms([master]) for _ in range(reps)]
+            r["stream_read_ms"] = round(med(sr), 5)
+            r["stream_read_GBs"] = round(master.numel() / (med(sr) * 1e-3) / 1e9, 1)
+            # the extract's line traffic (whole 128-byte lines of the first 128 bytes of a slot, or
+            # the whole dense ring) against the streaming rate of the same run
+            touched = min(slot, 128) * n + (stride + 3) * n
+            r["extract_line_GBs"] = round(touched / (med(ex) * 1e-3) / 1e9, 1)
+            r["extract_line_frac_of_stream_read"] = round(r["extract_line_GBs"] / r["stream_read_GBs"], 4)
+            batch = [(recs, n, bits, stride)]
+            for _ in range(args.warmup):
+                ctx.verify_batches_timed(batch)
+            vb = [ctx.verify_batches_timed(batch) for _ in range(reps)]
+            r["verify_batches_ms"] = round(med(vb), 5)
+            vf = lambda: ctx.verify_frames(master, slot, d_len, n, recs, status, bits)   # noqa: E731
+
+            def two():
+                ctx.extract_records(master, slot, d_len, n, recs, status)
+                ctx.verify_batches(batch)
+
+            for _ in range(args.warmup):
+                vf()
+                two()
+            torch.cuda.synchronize()
+            r["verify_frames_region_ms"] = round(med(region_ms(torch, vf, reps)), 5)
+            r["extract_verify_region_ms"] = round(med(region_ms(torch, two, reps)), 5)
+            r["mask_ms_by_difference"] = round(r["verify_frames_region_ms"] - r["extract_verify_region_ms"], 5)
+            # the mask kernel alone (idempotent: the bitmap stays what verify_frames left), between
+            # events: one launch (what the event pair itself costs is in it), and 20 back to back
+            mask = lambda: ctx.mask_status(status, n, bits)   # noqa: E731
+
+            def mask20():
+                for _ in range(20):
+                    mask()
+
+            for _ in range(args.warmup):
+                mask20()
+            torch.cuda.synchronize()
+            r["mask_ms"] = round(med(region_ms(torch, mask, reps)), 5)
+            r["mask_ms_per_launch_of_20"] = round(med(region_ms(torch, mask20, reps)) / 20, 5)
+            passed = int(np.unpackbits(bits.cpu().numpy().view(np.uint8)).sum())
+            r["frames_passed"] = passed
+            work = torch.empty_like(master)
+            br = []
+            for k in range(args.warmup + reps):
+                work.copy_(master)
+                t = ctx.br_process_timed(work, slot, d_len, d_if, n, act, ver, egr)
+                if k >= args.warmup:
+                    br.append(t)
+            r["br_process_ms"] = round(med(br), 5)
+            r["router_forwarded"] = int((act == 4).sum())
+            r["n_good"] = n_good
+            kernels = r["extract_ms"] + r["verify_batches_ms"] + r["mask_ms"]
+            r["frames_path_kernels_ms"] = round(kernels, 5)
+            r["frames_path_over_router"] = round(kernels / r["br_process_ms"], 4)
+            r["region_over_router"] = round(r["verify_frames_region_ms"] / r["br_process_ms"], 4)
+            del work
+        result["slots"][str(slot)] = r
+        del master, buf
+    ctx.close()
+    line = json.dumps(result)
+    print(line, flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(json.dumps(result, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
