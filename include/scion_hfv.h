@@ -202,6 +202,52 @@ int hfv_extract_records_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, 
 int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
                       void *recs, size_t stride, uint8_t *status, uint64_t *pass_bits, void *stream);
 
+/* ---- direction-aware frames: the AS-egress rule for frames from the internal link -------------
+ * The calls above apply one MAC-chaining rule, the AS-ingress rule of scion_as_ingress
+ * (path_processing.h:72-81): beta = SegID ^ MAC[0:2] for a Cons = 0 segment.  It holds for frames
+ * received on an external interface.  A frame that arrives over the AS-internal link was processed
+ * by a sibling router, which folded the MAC into the SegID already; the router verifies it in
+ * scion_as_egress (path_processing.h:140-142) with the SegID as it stands, whatever Cons, and
+ * chooses that rule where the receiving ifindex is in int_iface_map (xdp.c:129-131).  The *_rx calls
+ * take that ifindex per frame and write a normalised record for such frames: where status is 0,
+ * the frame is internal and its current InfoField has Cons = 0 (byte 0, bit 0), the record's SegID
+ * (InfoField bytes 2-3) is the frame's SegID ^ the current HopField's bytes 6-7 (MAC[0:2]), which
+ * the verify kernels' ingress rule undoes.  Every other byte, and every record of an external or
+ * Cons = 1 frame, is what hfv_extract_records writes.  The record verify itself is unchanged.
+ *
+ * What these calls do NOT do (the router, hfv_br_process, does):
+ *   - no ingress_map lookup and no VERDICT_NO_INTERFACE: any ifindex outside the set is external;
+ *   - no router-alert check (a hop field with alert flags is verified like any other);
+ *   - frames from the internal link whose AS-egress interface is not fwd_external (internal to
+ *     internal) get no MAC check at all in the reference (xdp.c:202-233); here they are judged by
+ *     the egress rule like every internal frame;
+ *   - hfv_verdict_counters keys by the AS-ingress IFID of the record, which is not the receiving
+ *     interface of an internal frame. */
+/* The membership test of int_iface_map as a set of at most HFV_BR_MAX_IFACES ifindices, held on
+ * the host in the ctx: pass cfg.int_ifaces[i].ifindex of the router's hfv_br_config (the set is
+ * independent of hfv_br_set_config).  n == 0 clears it.  n > HFV_BR_MAX_IFACES, or NULL with
+ * n > 0: -EINVAL, the set unchanged.  Takes effect for calls enqueued afterwards. */
+int hfv_ctx_set_internal_ifindices(hfv_ctx *ctx, const uint32_t *ifindex, size_t n);
+/* hfv_extract_records with the receiving interface: ingress_ifindex is a device uint32_t[n] (the
+ * array hfv_br_process takes), never written, no element at or past n read; frame i is internal
+ * iff ingress_ifindex[i] is in the ctx's set.  NULL, or an empty set: every frame is external and
+ * the outputs are byte-identical to hfv_extract_records. */
+int hfv_extract_records_rx(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                           const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride, uint8_t *status,
+                           void *stream);
+int hfv_extract_records_rx_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                                 const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride,
+                                 uint8_t *status, void *stream, float *kernel_ms);
+/* hfv_verify_frames over hfv_extract_records_rx: the same three launches on `stream`, no host
+ * synchronisation, no allocation, the same argument checks. */
+int hfv_verify_frames_rx(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                         const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride, uint8_t *status,
+                         uint64_t *pass_bits, void *stream);
+/* One frame on the host: hfv_frame_locate, the copy of the two fields and, for from_internal != 0,
+ * the normalisation above.  Returns the status; inf and hf are all zeros for a non-zero status;
+ * -EINVAL for NULL arguments.  The scalar counterpart of hfv_extract_records_rx. */
+int hfv_frame_extract(const uint8_t *frame, size_t len, int from_internal, uint8_t inf[8], uint8_t hf[12]);
+
 /* Verdict counts for the verify-only paths, modelled on record_verdict (xdp.c:54-70) but NOT
  * its layout: counters[slot][0] += packets that verified, counters[slot][1] += packets dropped
  * as VERDICT_INVALID_HF, where slot is the packet's AS-ingress interface (IFID & 0xff,

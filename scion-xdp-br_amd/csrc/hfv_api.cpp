@@ -205,6 +205,8 @@ struct hfv_ctx {
     // attached pinned router tables (hfv_ctx_attach_brconfig)
     const void *brmap = nullptr;
     uint32_t brmap_seq = 0xffffffffu;
+    // interfaces of the AS-internal link (hfv_ctx_set_internal_ifindices), for the *_rx frame calls
+    RxSet rx_set{};
     // dispatch timing (hfv_verify_records_timed)
     hipEvent_t tev[2] = {nullptr, nullptr};
     uint64_t *bat_clk = nullptr;   // device: hfv_verify_batches' block-0 clock stamps (hfv_debug_batches_clock)
@@ -834,10 +836,24 @@ static int frames_check(const hfv_ctx *ctx, const uint8_t *frames, size_t slot, 
     return 0;
 }
 
+// The set hfv_extract_records_rx / hfv_verify_frames_rx test ingress_ifindex[i] against: host state,
+// copied into the kernel arguments of every launch, so a change holds for calls enqueued after it.
+int hfv_ctx_set_internal_ifindices(hfv_ctx *ctx, const uint32_t *ifindex, size_t n)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n > kRxSetMax) return fail(-EINVAL, "%zu internal ifindices (at most %u)", n, kRxSetMax);
+    if (!ifindex && n) return fail(-EINVAL, "null ifindex list");
+    ctx->rx_set.n = (uint32_t)n;
+    for (size_t i = 0; i < kRxSetMax; ++i) ctx->rx_set.v[i] = i < n ? ifindex[i] : 0u;
+    return 0;
+}
+
 // The extract kernel needs LDS on every CU it runs on, which a running service grid holds until
 // it stops: like every other data-path call, these stop the service after its posted batches.
-int hfv_extract_records(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, void *recs,
-                        size_t stride, uint8_t *status, void *stream)
+// The direction-blind calls are the direction-aware ones without an ifindex array.
+int hfv_extract_records_rx(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                           const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride, uint8_t *status,
+                           void *stream)
 {
     if (!ctx) return fail(-EINVAL, "ctx is NULL");
     if (n == 0) return 0;
@@ -845,13 +861,14 @@ int hfv_extract_records(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const 
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
-    int e = launch_extract_records(frames, slot, len, n, (uint8_t *)recs, stride, ctx->inf_off, ctx->hf_off, status,
-                                   pick_stream(ctx, stream));
+    int e = launch_extract_records_rx(frames, slot, len, ingress_ifindex, ctx->rx_set, n, (uint8_t *)recs, stride,
+                                      ctx->inf_off, ctx->hf_off, status, pick_stream(ctx, stream));
     return e == hipSuccess ? 0 : hip_fail((hipError_t)e, "extract_records launch");
 }
 
-int hfv_extract_records_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
-                              void *recs, size_t stride, uint8_t *status, void *stream, float *kernel_ms)
+int hfv_extract_records_rx_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                                 const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride,
+                                 uint8_t *status, void *stream, float *kernel_ms)
 {
     if (!ctx || !kernel_ms) return fail(-EINVAL, "null argument");
     *kernel_ms = 0.0f;
@@ -862,16 +879,18 @@ int hfv_extract_records_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, 
     SVC_QUIESCE(ctx);
     for (int i = 0; i < 2; ++i)
         if (!ctx->tev[i]) HIP_TRY(hipEventCreate(&ctx->tev[i]));
-    int e = launch_extract_records(frames, slot, len, n, (uint8_t *)recs, stride, ctx->inf_off, ctx->hf_off, status,
-                                   pick_stream(ctx, stream), ctx->tev[0], ctx->tev[1]);
+    int e = launch_extract_records_rx(frames, slot, len, ingress_ifindex, ctx->rx_set, n, (uint8_t *)recs, stride,
+                                      ctx->inf_off, ctx->hf_off, status, pick_stream(ctx, stream), ctx->tev[0],
+                                      ctx->tev[1]);
     if (e != hipSuccess) return hip_fail((hipError_t)e, "extract_records launch");
     HIP_TRY(hipEventSynchronize(ctx->tev[1]));
     HIP_TRY(hipEventElapsedTime(kernel_ms, ctx->tev[0], ctx->tev[1]));
     return 0;
 }
 
-int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, void *recs,
-                      size_t stride, uint8_t *status, uint64_t *pass_bits, void *stream)
+int hfv_verify_frames_rx(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                         const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride, uint8_t *status,
+                         uint64_t *pass_bits, void *stream)
 {
     if (!ctx) return fail(-EINVAL, "ctx is NULL");
     if (n == 0) return 0;
@@ -883,13 +902,31 @@ int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const ui
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
     hipStream_t st = pick_stream(ctx, stream);
-    int e = launch_extract_records(frames, slot, len, n, (uint8_t *)recs, stride, ctx->inf_off, ctx->hf_off, status,
-                                   st);
+    int e = launch_extract_records_rx(frames, slot, len, ingress_ifindex, ctx->rx_set, n, (uint8_t *)recs, stride,
+                                      ctx->inf_off, ctx->hf_off, status, st);
     if (e != hipSuccess) return hip_fail((hipError_t)e, "extract_records launch");
     rc = batches_launch(ctx, &b, 1, st, nullptr, nullptr);
     if (rc) return rc;
     e = launch_mask_status(status, n, pass_bits, st);
     return e == hipSuccess ? 0 : hip_fail((hipError_t)e, "status mask launch");
+}
+
+int hfv_extract_records(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, void *recs,
+                        size_t stride, uint8_t *status, void *stream)
+{
+    return hfv_extract_records_rx(ctx, frames, slot, len, nullptr, n, recs, stride, status, stream);
+}
+
+int hfv_extract_records_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
+                              void *recs, size_t stride, uint8_t *status, void *stream, float *kernel_ms)
+{
+    return hfv_extract_records_rx_timed(ctx, frames, slot, len, nullptr, n, recs, stride, status, stream, kernel_ms);
+}
+
+int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, void *recs,
+                      size_t stride, uint8_t *status, uint64_t *pass_bits, void *stream)
+{
+    return hfv_verify_frames_rx(ctx, frames, slot, len, nullptr, n, recs, stride, status, pass_bits, stream);
 }
 
 // Diagnostic (not part of include/scion_hfv.h): the last step of hfv_verify_frames alone,

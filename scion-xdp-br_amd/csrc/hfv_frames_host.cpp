@@ -1,7 +1,8 @@
-// hfv_frames_host.cpp -- hfv_frame_locate: the frame parser (hfv_frame_parse.h) over one frame
-// in host memory, the scalar counterpart of the extract kernel as hfv_verify_macinput is of the
-// verify kernels.  No HIP dependency.
+// hfv_frames_host.cpp -- hfv_frame_locate and hfv_frame_extract: the frame parser
+// (hfv_frame_parse.h) over one frame in host memory, the scalar counterparts of the extract
+// kernels as hfv_verify_macinput is of the verify kernels.  No HIP dependency.
 #include <errno.h>
+#include <string.h>
 
 #include "hfv_frame_parse.h"
 #include "hfv_internal.h"
@@ -27,4 +28,24 @@ extern "C" int hfv_frame_locate(const uint8_t *frame, size_t len, uint32_t *inf_
     *inf_off = loc.status == hfv::kFrameOk ? loc.inf : 0u;
     *hf_off = loc.status == hfv::kFrameOk ? loc.hf : 0u;
     return loc.status;
+}
+
+// hfv_frame_extract: what the extract kernels write into a frame's record, on the host.  The two
+// fields of a frame that parses; for a frame from the internal link whose InfoField has Cons = 0,
+// the HopField's MAC[0:2] folded into the SegID (see hfv_extract_records_rx).
+extern "C" int hfv_frame_extract(const uint8_t *frame, size_t len, int from_internal, uint8_t inf[8], uint8_t hf[12])
+{
+    if (!frame || !inf || !hf) return hfv::fail(-EINVAL, "null argument");
+    const int end = len > 65536 ? 65536 : (int)len;   // as hfv_frame_locate
+    const hfv::FrameLoc loc = hfv::frame_locate(HostReader{frame}, end);
+    memset(inf, 0, 8);
+    memset(hf, 0, 12);
+    if (loc.status != hfv::kFrameOk) return loc.status;
+    memcpy(inf, frame + loc.inf, 8);
+    memcpy(hf, frame + loc.hf, 12);
+    if (from_internal && !(inf[0] & 1u)) {
+        inf[2] ^= hf[6];
+        inf[3] ^= hf[7];
+    }
+    return 0;
 }

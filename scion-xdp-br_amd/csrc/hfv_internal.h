@@ -309,6 +309,18 @@ int launch_br_process(const LaunchGeom &g, const DevState *st, uint8_t *pkts, si
 int launch_extract_records(const uint8_t *frames, size_t slot, const uint16_t *len, size_t n, uint8_t *recs,
                            size_t stride, uint32_t inf_off, uint32_t hf_off, uint8_t *status, void *stream,
                            void *ev_start = nullptr, void *ev_stop = nullptr);
+// The direction-aware extract (hfv_extract_records_rx): frame i is internal iff ingress_ifindex[i]
+// is one of set.v[0 .. set.n); the set travels by value in the kernel arguments.  A null
+// ingress_ifindex or an empty set launches the kernels of launch_extract_records.
+constexpr uint32_t kRxSetMax = HFV_BR_MAX_IFACES;
+struct RxSet {
+    uint32_t n;
+    uint32_t v[kRxSetMax];
+};
+int launch_extract_records_rx(const uint8_t *frames, size_t slot, const uint16_t *len, const uint32_t *ingress_ifindex,
+                              const RxSet &set, size_t n, uint8_t *recs, size_t stride, uint32_t inf_off,
+                              uint32_t hf_off, uint8_t *status, void *stream, void *ev_start = nullptr,
+                              void *ev_stop = nullptr);
 // pass_bits[i / 64] &= ballot(status[i] == 0), the last step of hfv_verify_frames
 int launch_mask_status(const uint8_t *status, size_t n, uint64_t *bits, void *stream);
 

@@ -84,6 +84,12 @@ def lib():
         "hfv_extract_records": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp]),
         "hfv_extract_records_timed": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, ctypes.POINTER(ctypes.c_float)]),
         "hfv_verify_frames": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp]),
+        "hfv_ctx_set_internal_ifindices": (i32, [vp, vp, sz]),
+        "hfv_extract_records_rx": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp]),
+        "hfv_extract_records_rx_timed": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp,
+                                               ctypes.POINTER(ctypes.c_float)]),
+        "hfv_verify_frames_rx": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]),
+        "hfv_frame_extract": (i32, [vp, sz, i32, vp, vp]),
         "hfv_ctx_describe": (i32, [vp, ctypes.c_char_p, sz]),
         "hfv_ctx_attach_keymap": (i32, [vp, ctypes.c_char_p]),
         "hfv_keymap_path": (i32, [ctypes.c_char_p, ctypes.c_char_p, sz]),
@@ -236,6 +242,18 @@ def frame_locate(frame_bytes):
     if rc < 0:
         _check(rc)
     return rc, inf.value, hf.value
+
+
+def frame_extract(frame_bytes, from_internal=False):
+    """hfv_frame_extract: (status, inf[8], hf[12]) of one Ethernet frame, as the extract kernels
+    write them into its record: the current InfoField and HopField (zeros unless status is
+    FRAME_OK), for from_internal with MAC[0:2] folded into the SegID of a Cons = 0 InfoField."""
+    buf = bytes(frame_bytes)
+    inf, hf = ctypes.create_string_buffer(8), ctypes.create_string_buffer(12)
+    rc = lib().hfv_frame_extract(buf, len(buf), int(bool(from_internal)), inf, hf)
+    if rc < 0:
+        _check(rc)
+    return rc, inf.raw, hf.raw
 
 
 def verify_macinput(macinput: bytes, expected: int, hop_key_bytes) -> bool:
@@ -496,6 +514,37 @@ class Ctx:
         frame i parsed (status 0) and its current hop field verifies."""
         _check(lib().hfv_verify_frames(self._h, _ptr(frames), slot, _ptr(lens), n, _ptr(recs), stride, _ptr(status),
                                        _ptr(pass_bits), _stream(stream)))
+
+    def set_internal_ifindices(self, ifindices):
+        """hfv_ctx_set_internal_ifindices: the ifindices of the AS-internal link (at most 16;
+        cfg.int_ifaces[i].ifindex of the router config), which the *_rx frame calls test each
+        frame's receiving ifindex against.  An empty list clears the set."""
+        vals = [int(x) for x in ifindices]
+        arr = (ctypes.c_uint32 * max(len(vals), 1))(*vals)
+        _check(lib().hfv_ctx_set_internal_ifindices(self._h, arr, len(vals)))
+
+    def extract_records_rx(self, frames, slot, lens, ingress_ifindex, n, recs, status, stride=FRAME_REC_STRIDE,
+                           stream=None):
+        """hfv_extract_records_rx: extract_records with the receiving ifindex per frame (device
+        u32[n], or None: every frame external).  A frame from an internal interface with a
+        Cons = 0 InfoField gets MAC[0:2] folded into its record's SegID (the AS-egress rule)."""
+        _check(lib().hfv_extract_records_rx(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
+                                            _ptr(recs), stride, _ptr(status), _stream(stream)))
+
+    def extract_records_rx_timed(self, frames, slot, lens, ingress_ifindex, n, recs, status, stride=FRAME_REC_STRIDE,
+                                 stream=None):
+        """extract_records_rx, waited for; returns the kernel's execution time in ms."""
+        ms = ctypes.c_float(0.0)
+        _check(lib().hfv_extract_records_rx_timed(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
+                                                  _ptr(recs), stride, _ptr(status), _stream(stream), ctypes.byref(ms)))
+        return ms.value
+
+    def verify_frames_rx(self, frames, slot, lens, ingress_ifindex, n, recs, status, pass_bits,
+                         stride=FRAME_REC_STRIDE, stream=None):
+        """hfv_verify_frames_rx: verify_frames over extract_records_rx; frames from the internal
+        link are judged by the router's AS-egress rule."""
+        _check(lib().hfv_verify_frames_rx(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
+                                          _ptr(recs), stride, _ptr(status), _ptr(pass_bits), _stream(stream)))
 
     def mask_status(self, status, n, pass_bits, stream=None):
         """Diagnostic (hfv_debug_mask_status): verify_frames' last step alone,

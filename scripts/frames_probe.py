@@ -11,11 +11,20 @@ plus a streaming read of the frame buffer (hfv_debug_stream_read, as bench.py us
 extract kernel's algorithmic bytes: per frame the 64-byte lines that hold the fields the parser
 reads, + 24 written + 3 of len/status.  Prints one JSON object and writes it to --out.
 
-  timeout -k 10 300 python scripts/frames_probe.py [--direct] [--extract-only] [--slots 2048,144]
+  timeout -k 10 300 python scripts/frames_probe.py [--direct] [--extract-only] [--slots 2048,144] [--rx]
 
 --direct places the frame buffer 8 bytes off a 16-byte boundary, which the staged kernel's 16-byte
 loads cannot take: the library then runs the direct kernel (every field read from global memory),
 the alternative of the A/B in profiles/ab_index.md.
+
+--rx adds, per slot under "rx", the direction-aware path (hfv_extract_records_rx /
+hfv_verify_frames_rx) with the mix's own ifindex array and BR 1's internal ifindices: its extract
+kernel timed alternately with hfv_extract_records_timed on the same frames (medians and their
+ratio), the frames it passes, and per frame its pass bit against the verdict hfv_br_process gives
+in the same run, over the frames decided by the MAC (the router's verdict is SCION_FORWARD or
+INVALID_HF, and a frame from the internal link has an AS-egress IFID with a fwd_external egress
+entry).  Every other field is what a run without --rx reports; the default --out becomes
+profiles/frames/frames_rx_probe.json.
 """
 import argparse
 import json
@@ -64,6 +73,59 @@ def region_ms(torch, fn, reps):
     return out
 
 
+def rx_leg(torch, hfv, ctx, cfg, internal_ifx, frames, tid, ifx, master, slot, d_len, d_if, n, recs, status, bits, ver,
+           warmup, reps):
+    """The direction-aware path on the frames of one slot size; `ver` holds hfv_br_process's
+    verdicts of this run on the same frames (None: no comparison)."""
+    ctx.set_internal_ifindices(internal_ifx)
+    r = {"internal_ifindices": internal_ifx, "frames_from_internal": int(np.isin(ifx, internal_ifx).sum())}
+    plain = lambda: ctx.extract_records_timed(master, slot, d_len, n, recs, status)   # noqa: E731
+    aware = lambda: ctx.extract_records_rx_timed(master, slot, d_len, d_if, n, recs, status)   # noqa: E731
+    for _ in range(warmup):
+        plain()
+        aware()
+    a, b = [], []
+    for _ in range(reps):                                # alternating: both see the same machine
+        a.append(plain())
+        b.append(aware())
+    r["extract_ms"] = round(med(a), 5)
+    r["extract_ms_min_max"] = [round(min(a), 5), round(max(a), 5)]
+    r["extract_rx_ms"] = round(med(b), 5)
+    r["extract_rx_ms_min_max"] = [round(min(b), 5), round(max(b), 5)]
+    r["extract_rx_over_extract"] = round(med(b) / med(a), 4)
+    if ver is None:
+        return r
+    ctx.verify_frames_rx(master, slot, d_len, d_if, n, recs, status, bits)
+    torch.cuda.synchronize()
+    got = hfv.bits_to_bool(bits.cpu().numpy().view(np.uint64), n)
+    r["frames_passed"] = int(got.sum())
+    # the frames decided by the MAC, by the router kernel's verdicts; the fields of each template
+    # frame by the host parser
+    fields = [hfv.frame_extract(f[:slot], False) for f in frames]
+    cons = np.array([st == 0 and bool(i[0] & 1) for st, i, h in fields])
+    egr = np.array([0 if st else int.from_bytes(h[4:6] if i[0] & 1 else h[2:4], "big") for st, i, h in fields])
+    ext_ifid = [int(cfg.egress[i].ifid) for i in range(cfg.n_egress) if cfg.egress[i].fwd_external]
+    v = ver.cpu().numpy()
+    decided = np.isin(v, [hfv.VERDICT["SCION_FORWARD"], hfv.VERDICT["INVALID_HF"]])
+    internal = np.isin(ifx, internal_ifx)
+    sel = decided & (~internal | np.isin(egr[tid], ext_ifid))
+    fwd = v == hfv.VERDICT["SCION_FORWARD"]
+    r["mac_decided"] = int(sel.sum())
+    r["mac_decided_internal"] = int((sel & internal).sum())
+    r["mac_decided_internal_noncons"] = int((sel & internal & ~cons[tid]).sum())
+    r["mac_decided_invalid_hf"] = int((sel & ~fwd).sum())
+    r["agree_with_router"] = int((got[sel] == fwd[sel]).sum())
+    r["agree_with_router_internal"] = int((got[sel & internal] == fwd[sel & internal]).sum())
+    r["router_forward_not_passed"] = int((fwd & ~got).sum())     # over all frames, for the record
+    # the direction-blind call on the same frames, against the same verdicts
+    ctx.verify_frames(master, slot, d_len, n, recs, status, bits)
+    torch.cuda.synchronize()
+    blind = hfv.bits_to_bool(bits.cpu().numpy().view(np.uint64), n)
+    r["verify_frames_passed"] = int(blind.sum())
+    r["verify_frames_agree_with_router"] = int((blind[sel] == fwd[sel]).sum())
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -72,8 +134,11 @@ def main():
     ap.add_argument("--slots", default="2048,144")
     ap.add_argument("--direct", action="store_true", help="misalign the frame buffer: the direct kernel")
     ap.add_argument("--extract-only", action="store_true", help="A/B runs: the extract kernel alone")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "frames", "frames_probe.json"))
+    ap.add_argument("--rx", action="store_true", help="add the direction-aware path (see above)")
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "frames", "frames_rx_probe.json" if args.rx else "frames_probe.json")
     args.extract_only |= args.direct   # the other legs want the aligned buffer
     import torch
     import bench
@@ -85,8 +150,10 @@ def main():
     tmpl, tid, lens, ifx, n_good = bench.br_batch(n, 0)
     ctx = hfv.Ctx(0)
     ctx.key_add(0, TP.KEYS[1])
-    ctx.br_set_config(TP.br_config("br1"))
+    cfg = TP.br_config("br1")
+    ctx.br_set_config(cfg)
     ctx.set_record_layout(0, 8)
+    internal_ifx = [int(cfg.int_ifaces[i].ifindex) for i in range(cfg.n_int_ifaces)]
     stride = hfv.FRAME_REC_STRIDE
     d_tid = torch.from_numpy(tid.astype(np.int64)).cuda()
     d_if = torch.from_numpy(ifx.view(np.int32)).cuda()
@@ -181,6 +248,9 @@ def main():
             r["frames_path_over_router"] = round(kernels / r["br_process_ms"], 4)
             r["region_over_router"] = round(r["verify_frames_region_ms"] / r["br_process_ms"], 4)
             del work
+        if args.rx:
+            r["rx"] = rx_leg(torch, hfv, ctx, cfg, internal_ifx, frames, tid, ifx, master, slot, d_len, d_if, n, recs,
+                             status, bits, None if args.extract_only else ver, args.warmup, reps)
         result["slots"][str(slot)] = r
         del master, buf
     ctx.close()
