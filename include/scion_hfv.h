@@ -373,56 +373,8 @@ int hfv_gen_records(hfv_ctx *ctx, void *recs, size_t stride, size_t n, uint64_t 
  * The BPF maps become one configuration struct.  bpf_fib_lookup (a kernel helper) is
  * replaced by a static next-hop table with longest-prefix match; an address with no route
  * behaves like BPF_FIB_LKUP_RET_NOT_FWDED.  Addresses and ports are in wire byte order. */
-#define HFV_AF_INET 2
-#define HFV_AF_INET6 10
-#define HFV_BR_MAX_IFACES 16
-#define HFV_BR_MAX_ROUTES 64
-#define HFV_BR_MAX_TXPORTS 128
-#define HFV_BR_COUNTERS 11         /* enum counter (common.h:40-53) */
-#define HFV_BR_STATS_IFINDEX 64    /* counters kept for ingress ifindex < 64 */
-#define HFV_BR_ACTION_RETRY 0xff   /* internal to the windowed host path; never returned */
-
-struct hfv_br_int_iface {          /* int_iface_map: ifindex -> internal address (common.h:116-128) */
-    uint32_t ifindex;
-    uint32_t family;
-    uint8_t addr[16];              /* IPv4 in addr[0..3] */
-    uint8_t port[2];
-    uint8_t pad[2];
-};
-struct hfv_br_ingress {            /* ingress_map: {dst addr, dst port, ifindex} -> AS interface id (common.h:73-84) */
-    uint32_t ifindex;
-    uint32_t family;
-    uint8_t addr[16];
-    uint8_t port[2];
-    uint8_t pad[2];
-    uint32_t ifid;
-};
-struct hfv_br_egress {             /* egress_map: ifid -> fwd_info (common.h:131-145) */
-    uint32_t ifid;
-    uint32_t fwd_external;         /* 1: ext_link {remote, local}, 0: sibling BR {remote = its internal address} */
-    uint32_t family;
-    uint8_t remote[16];
-    uint8_t local[16];
-    uint8_t remote_port[2];
-    uint8_t local_port[2];
-};
-struct hfv_br_route {              /* replaces bpf_fib_lookup (fib_lookup.h:74-261) */
-    uint32_t family;
-    uint8_t prefix[16];
-    uint32_t prefix_len;
-    int32_t ret;                   /* BPF_FIB_LKUP_RET_*: 0 success, 1-3 drop, 4-8 pass */
-    uint32_t ifindex;
-    uint8_t smac[6];
-    uint8_t dmac[6];
-};
-struct hfv_br_config {
-    uint32_t n_int_ifaces, n_ingress, n_egress, n_routes, n_tx_ports;
-    struct hfv_br_int_iface int_ifaces[HFV_BR_MAX_IFACES];
-    struct hfv_br_ingress ingress[HFV_BR_MAX_IFACES];
-    struct hfv_br_egress egress[HFV_BR_MAX_IFACES];
-    struct hfv_br_route routes[HFV_BR_MAX_ROUTES];
-    uint32_t tx_ports[HFV_BR_MAX_TXPORTS];   /* tx_port_map: ifindices a redirect may target */
-};
+/* HFV_AF_*, HFV_BR_* limits and struct hfv_br_config with its entry types */
+#include "hfv_br_config.h"
 
 /* Install the router tables (copied; takes effect for batches enqueued afterwards).  Detaches
  * a pinned config attached with hfv_ctx_attach_brconfig. */

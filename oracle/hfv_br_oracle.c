@@ -19,10 +19,17 @@
  *   - the egress HF check uses the current (not switched-to) info field (path_processing.h:142);
  *   - the checksum residuals are u64 sums of little-endian loads of network-order fields and
  *     FOLD_CHECKSUM is applied to ~check + residual + 1 (rewrite.h:35-40, 61-65, 103-106);
- *   - an unknown bpf_fib_lookup return code is treated as success (fib_lookup.h:100-114).
+ *   - an unknown bpf_fib_lookup return code is treated as success (fib_lookup.h:100-114), with
+ *     the route's MACs and ifindex (the contract of hfv_br_route.ret, hfv_br_config.h).  The
+ *     kernel helper returns no such code, so the comparison with the reference's own program
+ *     (ref_br.c, tests/test_br_ref.py) covers results 0..8 only.
  * One deviation, shared with the GPU kernel: the per-CPU scratchpad is zeroed per packet,
  * so seg_id[1] is 0 when parse_scion_path does not set it (in XDP it holds whatever the
  * previous packet on that CPU left there).
+ *
+ * Pinned bit for bit against br/src/bpf/xdp.c itself, compiled as host code (oracle/Makefile,
+ * ref_br.c): tests/test_br_ref.py.  feat_off ORC_BR_NO_IPV4 and ORC_BR_NO_SCION_PATH model builds
+ * the reference does not compile as and stay restated from the text only.
  */
 #include <string.h>
 

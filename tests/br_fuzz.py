@@ -197,3 +197,159 @@ def options_shift_batch(hops, br="br1"):
             ifis.append(ifi)
     frames, lens = T.to_slots(frames_l)
     return frames, lens, np.array(ifis, dtype=np.uint32), len(mine)
+
+
+# ---- table fuzz: mutated router tables ---------------------------------------------------------
+# Every topology table (br_topo.br_config) is tie-free, has host routes only, a sibling interface
+# for every internal route and every redirect target in tx_ports; these mutations reach what such
+# tables never do: the longest-prefix rule, route results, missing interfaces, family checks and
+# the u16 truncation of the ingress key.
+ROUTE_IFINDICES = [1, 3, 5, 7, 2, 9, 63, 64, 100, 127, 128, 200, 70000]   # known, unknown, >= 64, >= 128, > 65535
+UNDEFINED_RETS = [9, 11, 255, -1]
+TABLE_FUZZ_N = 1024          # 16 tiles of 64 frames: the smallest batch whose tiles still mix verdicts
+TABLE_FUZZ_SLOT = 256
+TABLE_FUZZ_BATCH_SEED = 4           # a batch in which both families carry router-alert frames
+TABLE_FUZZ_SEED = 2024
+TABLE_FUZZ_COUNT = 64
+
+
+def _clone(cfg):
+    return type(cfg).from_buffer_copy(bytes(cfg))
+
+
+def _drop(arr, n, i):
+    for j in range(i, n - 1):
+        arr[j] = type(arr[j]).from_buffer_copy(bytes(arr[j + 1])) if hasattr(arr[j], "_fields_") else arr[j + 1]
+
+
+def _flip_family(f):
+    return 10 if f == 2 else 2
+
+
+def mutate_config(rng, cfg):
+    """A copy of cfg with 1-3 random mutations; .mutations names them.  Deterministic in rng."""
+    c = _clone(cfg)
+    names = []
+    for _ in range(int(rng.integers(1, 4))):
+        m = int(rng.integers(0, 9))
+        if m == 0 and c.n_routes:
+            r = c.routes[int(rng.integers(0, c.n_routes))]
+            r.ret = int(rng.integers(0, 9))
+            names.append("route ret %d" % r.ret)
+        elif m == 1 and c.n_routes:
+            r = c.routes[int(rng.integers(0, c.n_routes))]
+            full = 32 if r.family == 2 else 128
+            r.prefix_len = int(rng.choice([0, 1, 7, 8, 9, 24, 31, 32, 33, 64, 127, 128, 129, 139, full, full - 1]))
+            names.append("route prefix_len %d" % r.prefix_len)
+        elif m == 2 and c.n_routes:
+            r = c.routes[int(rng.integers(0, c.n_routes))]
+            r.ifindex = int(rng.choice(ROUTE_IFINDICES))
+            names.append("route ifindex %d" % r.ifindex)
+        elif m == 3 and 0 < c.n_routes < len(c.routes):
+            i = int(rng.integers(0, c.n_routes))
+            old, new = c.routes[i], c.routes[c.n_routes]
+            c.routes[c.n_routes] = type(old).from_buffer_copy(bytes(old))
+            full = 32 if old.family == 2 else 128
+            new.prefix_len = int(rng.choice([old.prefix_len, old.prefix_len, max(0, min(old.prefix_len, full) - 8), 0]))
+            new.ret = int(rng.choice([0, 0, 1, 2, 3, 4, 7]))
+            new.ifindex = int(rng.choice(ROUTE_IFINDICES))
+            new.smac[0], new.dmac[5] = 0x06, int(rng.integers(0, 256))
+            first = bool(rng.integers(0, 2))
+            if first:          # in front of the route it shadows: the added one wins a tie
+                keep = type(old).from_buffer_copy(bytes(old))
+                c.routes[i] = type(old).from_buffer_copy(bytes(new))
+                c.routes[c.n_routes] = keep
+            c.n_routes += 1
+            names.append("added route /%d ret %d if %d %s" % (new.prefix_len, new.ret, new.ifindex,
+                                                              "first" if first else "last"))
+        elif m == 4:
+            if rng.integers(0, 2) and c.n_int_ifaces:
+                e = c.int_ifaces[int(rng.integers(0, c.n_int_ifaces))]
+                e.family = _flip_family(e.family)
+                names.append("int_iface %d family" % e.ifindex)
+            elif c.n_egress:
+                e = c.egress[int(rng.integers(0, c.n_egress))]
+                e.family = _flip_family(e.family)
+                names.append("egress %d family" % e.ifid)
+        elif m == 5 and c.n_egress:
+            e = c.egress[int(rng.integers(0, c.n_egress))]
+            e.fwd_external = 0 if e.fwd_external else 1
+            names.append("egress %d fwd_external %d" % (e.ifid, e.fwd_external))
+        elif m == 6:
+            t = int(rng.integers(0, 4))
+            arr, cnt = [(c.egress, "n_egress"), (c.int_ifaces, "n_int_ifaces"), (c.routes, "n_routes"),
+                        (c.tx_ports, "n_tx_ports")][t]
+            n = getattr(c, cnt)
+            if n:
+                i = int(rng.integers(0, n))
+                _drop(arr, n, i)
+                setattr(c, cnt, n - 1)
+                names.append("%s minus entry %d" % (cnt, i))
+        elif m == 7 and c.n_ingress:
+            e = c.ingress[int(rng.integers(0, c.n_ingress))]
+            e.ifindex += 65536
+            names.append("ingress ifindex %d" % e.ifindex)
+        elif m == 8 and c.n_ingress:
+            e = c.ingress[int(rng.integers(0, c.n_ingress))]
+            e.ifid = int(rng.choice([1, 2, 3, 0, 258, 65537]))
+            names.append("ingress ifid %d" % e.ifid)
+    c.mutations = names
+    return c
+
+
+def config_cases(v6, count=TABLE_FUZZ_COUNT, seed=TABLE_FUZZ_SEED):
+    """`count` mutated copies of br_config("br1", v6); every route result stays in 0..8, where the
+    reference program defines the outcome."""
+    rng = np.random.default_rng([seed, int(v6)])
+    base = T.br_config("br1", v6)
+    return [mutate_config(rng, base) for _ in range(count)]
+
+
+def config_cases_undefined_ret(v6, seed=TABLE_FUZZ_SEED):
+    """Mutated tables with one route result outside 0..8 (hfv_br_config.h: treated as success).
+    The reference program has no defined behaviour there, so these are judged by the oracle."""
+    rng = np.random.default_rng([seed, int(v6), 9])
+    base = T.br_config("br1", v6)
+    out = []
+    for ret in UNDEFINED_RETS:
+        for i in range(base.n_routes):
+            c = mutate_config(rng, base) if i % 2 else _clone(base)
+            if c.n_routes == 0:
+                c = _clone(base)
+            c.routes[min(i, c.n_routes - 1)].ret = ret
+            c.mutations = getattr(c, "mutations", []) + ["route %d ret %d" % (i, ret)]
+            out.append(c)
+    return out
+
+
+def table_fuzz_batch(hops, v6, slot=TABLE_FUZZ_SLOT):
+    """The one frame batch every table case runs on."""
+    return fuzz_batch(hops, "br1", v6, TABLE_FUZZ_N, TABLE_FUZZ_BATCH_SEED, slot=slot)
+
+
+def lpm_route(cfg, family, addr):
+    """Index of the route the documented rule gives (longest prefix on (family, dst), the first
+    entry wins a tie), -1 for none; in plain integers, independent of the C and HIP code."""
+    best, width = -1, 32 if family == 2 else 128
+    dst = int.from_bytes(bytes(addr), "big")
+    for i in range(cfg.n_routes):
+        r = cfg.routes[i]
+        if r.family != family or r.prefix_len > width:
+            continue
+        if r.prefix_len and (int.from_bytes(bytes(r.prefix), "big") ^ dst) >> (128 - r.prefix_len):
+            continue
+        if best < 0 or r.prefix_len > cfg.routes[best].prefix_len:
+            best = i
+    return best
+
+
+def missing_sibling_interface(cfg):
+    """True if a sibling entry of egress_map routes out of an interface that is not in
+    int_iface_map (fib_lookup_egress_br then ends in VERDICT_ABORT)."""
+    ints = {cfg.int_ifaces[i].ifindex for i in range(cfg.n_int_ifaces)}
+    for i in range(cfg.n_egress):
+        e = cfg.egress[i]
+        r = lpm_route(cfg, e.family, e.remote) if not e.fwd_external else -1
+        if r >= 0 and cfg.routes[r].ret == 0 and cfg.routes[r].ifindex not in ints:
+            return True
+    return False

@@ -18,6 +18,11 @@ Sources of truth, in order:
   * ref_random.npz: the REFERENCE aes.c's verify bitmaps and CMAC tags on the random inputs of
     tests/orc.random_cases(), so that tests/test_oracle.py's random comparison also runs where
     the reference build is absent.
+  * br_ref.npz: the REFERENCE router program (br/src/bpf/xdp.c built as host code,
+    oracle/_ref/librefbr.so) on the table-fuzz batch of tests/br_fuzz.py: 1024 frames per
+    family under 8 mutated router tables per family that reach all 11 verdicts between them.
+    Refused unless the oracle router agrees on every byte.  `make_golden.py br_ref` writes
+    this fixture alone.
 """
 import ctypes
 import json
@@ -237,7 +242,72 @@ def make_ref_random():
     print(f"ref_random.npz: {len(recs)} random records x 2 key rules, {len(datas)} CMAC lengths x 2 functions")
 
 
+BR_REF_TABLES = 8
+
+
+def br_ref_inputs():
+    """(frames[2, n, slot], lens[2, n], ifidx[2, n], cases[2][...]): the table-fuzz batch and all
+    table cases per family (index 0 IPv4, 1 IPv6)."""
+    for p in (os.path.join(ROOT, "tests"), os.path.join(ROOT, "scion-xdp-br_amd")):
+        if p not in sys.path:
+            sys.path.insert(0, p)
+    import br_fuzz as F
+    import br_topo as T
+    import orc
+    mac = lambda k, m: orc.cmac(m, k)   # noqa: E731
+    frames, lens, ifidx, cases = [], [], [], []
+    for v6 in (False, True):
+        brs = {b: T.OracleBR(T.br_config(b, v6)) for b in ("br1", "br2", "br3")}
+        f, ln, ifi = F.table_fuzz_batch(F.hop_inputs(brs, v6, mac), v6)
+        frames.append(f), lens.append(ln), ifidx.append(ifi), cases.append(F.config_cases(v6))
+    return np.array(frames), np.array(lens), np.array(ifidx), cases
+
+
+def make_br_ref():
+    frames, lens, ifidx, cases = br_ref_inputs()   # also puts tests/ and the package on sys.path
+    import br_topo as T
+    import orc
+    assert orc.ref_br_available(), "build the reference router first: make -C oracle"
+    hk = orc.hop_key(T.KEYS[1])
+    cfgs, diffs, acts, verds, egrs, stats = [], [], [], [], [], []
+    for fam in range(2):
+        res = []
+        for c in cases[fam]:
+            out = frames[fam].copy()
+            r = orc.ref_br_process(out, lens[fam], ifidx[fam], c, hk)
+            mine = frames[fam].copy()
+            orc.assert_br_equal(orc.br_process(mine, lens[fam], ifidx[fam], c, hk), mine, r, out,
+                                "oracle != reference, family %d, %s" % (fam, c.mutations))
+            res.append((out, r))
+        # greedy cover of the 11 verdicts, rarest first through "most new values"; then the
+        # tables with the most UNDERLAY_MISMATCH / FIB_LKUP_DROP frames
+        seen, pick = set(), []
+        while len(pick) < BR_REF_TABLES:
+            def gain(i):
+                v = res[i][1][1]
+                return (len(set(np.unique(v).tolist()) - seen), int(((v == 50) | (v == 65)).sum()))
+            best = max((i for i in range(len(res)) if i not in pick), key=lambda i: (gain(i), -i))
+            pick.append(best)
+            seen |= set(np.unique(res[best][1][1]).tolist())
+        assert len(seen) == 11, sorted(seen)
+        cfgs.append([np.frombuffer(bytes(cases[fam][i]), dtype=np.uint8) for i in pick])
+        diffs.append([res[i][0] ^ frames[fam] for i in pick])
+        acts.append([res[i][1][0] for i in pick])
+        verds.append([res[i][1][1] for i in pick])
+        egrs.append([res[i][1][2] for i in pick])
+        stats.append([res[i][1][3] for i in pick])
+        print("br_ref family %d: tables %s" % (fam, pick))
+    path = os.path.join(HERE, "br_ref.npz")
+    np.savez_compressed(path, frames=frames, lens=lens, ifidx=ifidx, cfgs=np.array(cfgs),
+                        frames_out_xor=np.array(diffs), action=np.array(acts), verdict=np.array(verds),
+                        egress=np.array(egrs), stats=np.array(stats), key0=np.frombuffer(T.KEYS[1], dtype=np.uint8))
+    print("br_ref.npz: %d bytes" % os.path.getsize(path))
+
+
 def main():
+    if sys.argv[1:] == ["br_ref"]:
+        return make_br_ref()
+    make_br_ref()
     make_ref_random()
     kat = make_kat()
     with open(os.path.join(HERE, "kat.json"), "w") as f:

@@ -1,5 +1,6 @@
 """ctypes access to the CPU checker (oracle/libhfvoracle.so) and, when it was built, the
-reference's own AES compiled from /root/reference (oracle/_ref/libaesref.so).
+reference's own AES (oracle/_ref/libaesref.so) and its own router program
+(oracle/_ref/librefbr*.so, driven by oracle/ref_br.c), compiled from the reference sources.
 
 TEST INFRASTRUCTURE ONLY -- imported by tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg, never by the product package.
@@ -15,6 +16,9 @@ ORACLE_DIR = os.path.join(ROOT, "oracle")
 # HFV_ORACLE_SO: another build of the same checker (the sanitizer build, tests/test_sanitize.py)
 ORACLE_SO = os.environ.get("HFV_ORACLE_SO") or os.path.join(ORACLE_DIR, "libhfvoracle.so")
 REF_SO = os.path.join(ORACLE_DIR, "_ref", "libaesref.so")
+REFBR_SO = {(True, False): os.path.join(ORACLE_DIR, "_ref", "librefbr.so"),        # (hf_check, no_ipv6)
+            (False, False): os.path.join(ORACLE_DIR, "_ref", "librefbr_nohf.so"),
+            (True, True): os.path.join(ORACLE_DIR, "_ref", "librefbr_no6.so")}
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 SEED_RECORDS = 0x5C100001
@@ -162,6 +166,71 @@ def br_process(frames, lens, ifidx, cfg, key0_hop_key=None, stats=None, hf_check
                                  ctypes.byref(cfg), key, _vp(action), _vp(verdict), _vp(egress), _vp(stats),
                                  ctypes.c_int(1 if hf_check else 0), ctypes.c_uint32(feat_off))
     return action, verdict, egress, stats
+
+
+_refbr = {}
+_sbox = None
+
+
+def _refbr_lib(hf_check=True, no_ipv6=False):
+    k = (bool(hf_check), bool(no_ipv6))
+    if k not in _refbr:
+        so = REFBR_SO.get(k)
+        L = None
+        if so and os.path.exists(so) and reference() is not None:
+            L = ctypes.CDLL(so)
+            assert L.refbr_build_flags() == 1 | (0 if k[1] else 2) | 4 | (8 if k[0] else 0), so
+        _refbr[k] = L
+    return _refbr[k]
+
+
+def ref_br_available(hf_check=True, no_ipv6=False):
+    """Whether the reference router program was built in the given variant (the reference
+    compiles with ENABLE_HF_CHECK off or ENABLE_IPV6 off, not with both handled here, and not
+    with ENABLE_IPV4 or ENABLE_SCION_PATH off)."""
+    return _refbr_lib(hf_check, no_ipv6) is not None
+
+
+def ref_br_process(frames, lens, ifidx, cfg, key0_hop_key=None, hf_check=True, no_ipv6=False, stats=None,
+                   carry=False):
+    """The reference's own border_router() (br/src/bpf/xdp.c built as host code) over
+    frames[n, slot] in place; returns what br_process returns, or None when the library was not
+    built.  carry=True keeps the scratchpad across the frames of this call (a per-CPU map)
+    instead of zeroing it per frame.  Single-threaded."""
+    global _sbox
+    L = _refbr_lib(hf_check, no_ipv6)
+    if L is None:
+        return None
+    if _sbox is None:
+        _sbox = (ctypes.c_uint8 * 256).in_dll(reference(), "AES_SBox")
+    n, slot = frames.shape
+    assert frames.dtype == np.uint8 and frames.flags.c_contiguous
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    ifidx = np.ascontiguousarray(ifidx, dtype=np.uint32)
+    action = np.zeros(n, dtype=np.uint8)
+    verdict = np.zeros(n, dtype=np.uint8)
+    egress = np.zeros(n, dtype=np.int32)
+    if stats is None:
+        stats = np.zeros(BR_STATS_SHAPE, dtype=np.uint64)
+    key = ctypes.create_string_buffer(bytes(key0_hop_key), 192) if key0_hop_key is not None else None
+    L.refbr_set_carry(ctypes.c_int(1 if carry else 0))
+    try:
+        rc = L.refbr_process(_vp(frames), ctypes.c_size_t(slot), _vp(lens), _vp(ifidx), ctypes.c_size_t(n),
+                             ctypes.byref(cfg), key, _vp(action), _vp(verdict), _vp(egress), _vp(stats), _sbox)
+    finally:
+        L.refbr_set_carry(ctypes.c_int(0))
+    assert rc == 0, "no packet buffer below 4 GiB"
+    return action, verdict, egress, stats
+
+
+def assert_br_equal(got, got_frames, want, want_frames, what=""):
+    """(action, verdict, egress, stats) and every byte of every slot equal; names the first frame."""
+    ga, gv, ge, gs = got
+    wa, wv, we, ws = want
+    bad = np.nonzero((ga != wa) | (gv != wv) | (ge != we) | (got_frames != want_frames).any(axis=1))[0]
+    assert bad.size == 0, "%s: %d frames differ, first %d: got (%d,%d,%d) want (%d,%d,%d)" % (
+        what, bad.size, bad[0], ga[bad[0]], gv[bad[0]], ge[bad[0]], wa[bad[0]], wv[bad[0]], we[bad[0]])
+    assert (np.asarray(gs).reshape(BR_STATS_SHAPE) == np.asarray(ws).reshape(BR_STATS_SHAPE)).all(), what + ": counters"
 
 
 def load_golden(name):

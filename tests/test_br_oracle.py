@@ -3,9 +3,9 @@ reference's own PTF expectations (br/test/ptf_tests/tests.py), re-derived from t
 path rules because scapy/scapy_scion/ptf are not installed; and the verdict of every
 process_packet exit (br/src/bpf/xdp.c:98-283) on hand-made frames.
 
-The BPF program itself cannot be built here (no clang BPF target / libbpf), so beyond the
-PTF scenarios the oracle's quirk handling is pinned by reading xdp.c/parser.h/
-path_processing.h/rewrite.h only ("parity partially pinned").
+The BPF object cannot be built here (no clang BPF target / libbpf); the program's C text is
+compiled as host code instead and tests/test_br_ref.py repeats every call of this module against
+it.
 """
 import struct
 

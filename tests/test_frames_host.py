@@ -222,6 +222,30 @@ def test_truncation(kind, v6):
         prev = got[0]
 
 
+@pytest.mark.skipif(not orc.ref_br_available(), reason="reference router not built (oracle/_ref)")
+def test_status_is_the_reference_programs_parse_verdict():
+    """The same claim held against the reference's own router program (br/src/bpf/xdp.c built as
+    host code, orc.ref_br_process): on the mutation batches above and on every truncation of the
+    frames of test_truncation, a non-zero status is the verdict that program records."""
+    hk = orc.hop_key(T.KEYS[1])
+    for br, v6 in CASES:
+        frames, lens, ifidx, got, _, _ = batch(br, v6)
+        verdict = orc.ref_br_process(frames.copy(), lens, ifidx, T.br_config(br, v6), hk)[1]
+        st = np.array([g[0] for g in got])
+        assert np.array_equal(verdict[st != OK], st[st != OK]), (br, v6)
+        assert (st[verdict == V["NOT_SCION"]] == NOT_SCION).all()
+    for v6 in (False, True):
+        for kind in ("down", "seg_switch"):
+            ing_enc, _, _, ifi = T.encaps(1, 2, v6)
+            frame = ing_enc.frame(P.scion_header(P.ptf_path(kind, 1, 2, T.KEYS, seed=5, mac_fn=MAC).pack()))
+            rows, _ = T.to_slots([frame] * (len(frame) + 1), slot=256)
+            lens = np.arange(len(frame) + 1, dtype=np.uint16)
+            st = np.array([locate(frame, ln)[0] for ln in lens])
+            verdict = orc.ref_br_process(rows, lens, np.full(len(lens), ifi, np.uint32), T.br_config("br1", v6), hk)[1]
+            assert np.array_equal(verdict[st != OK], st[st != OK]), (kind, v6)
+            assert (st != OK).sum() >= 100 and verdict[-1] == V["SCION_FORWARD"]
+
+
 def test_frame_locate_arguments():
     L = hfv.lib()
     u = hfv.ctypes.c_uint32()
