@@ -23,6 +23,11 @@ Sources of truth, in order:
     family under 8 mutated router tables per family that reach all 11 verdicts between them.
     Refused unless the oracle router agrees on every byte.  `make_golden.py br_ref` writes
     this fixture alone.
+  * hf_bits.npz: the REFERENCE aes.c's verify bitmaps on the corpus of tests/hf_bits.py (passing
+    records with every don't-care bit set, and single-bit flips of sixteen of them; both key
+    rules, three record layouts, full and even-slots key table), with the SHA-256 of the corpus
+    bytes.  Refused unless the reference's soft path, its AES-NI path, the oracle and the
+    corpus' own rule agree.  `make_golden.py hf_bits` writes this fixture alone.
 """
 import ctypes
 import json
@@ -304,10 +309,46 @@ def make_br_ref():
     print("br_ref.npz: %d bytes" % os.path.getsize(path))
 
 
+def make_hf_bits():
+    """hf_bits.npz: the REFERENCE aes.c's verify bitmaps on the corpus of tests/hf_bits.py, for
+    both key rules and the three record layouts (and under KEYSEL_IFID with only the even slots
+    installed), with the SHA-256 of the corpus bytes.  Data only: bitmaps and hashes."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hf_bits as HB
+    import orc
+    raw = HB.raw_keys()
+    hk, valid = orc.key_table(raw)
+    out = {"sha256": np.zeros((2, len(HB.LAYOUTS), 32), dtype=np.uint8)}
+    for keysel in (0, 1):
+        for j, layout in enumerate(HB.LAYOUTS):
+            c = HB.corpus(keysel, layout)
+            view, n = HB.at_default_offsets(c.recs, layout), len(c.recs)
+            cases = [("bits_%d_%d" % (keysel, j), valid, c.passes)]
+            if keysel == 1:
+                cases.append(("partial_%d" % j, HB.partial_valid(), HB.partial_passes(c)))
+            for name, v, passes in cases:
+                soft, hw = (orc.ref_verify_records(view, raw, hk, v, keysel, aesni=a, stride=layout[2], n=n)
+                            for a in (0, 1))
+                assert soft is not None, "build the reference first: make -C oracle"
+                ours = orc.verify_records(view, hk, v, keysel, stride=layout[2], n=n)
+                rule = HB.bitmap(passes)
+                assert np.array_equal(soft, hw), (name, "reference soft vs AES-NI disagree")
+                assert np.array_equal(soft, ours), (name, "oracle verify != reference verify")
+                assert np.array_equal(soft, rule), (name, "the rule != reference verify")
+                out[name] = soft
+            out["sha256"][keysel, j] = np.frombuffer(HB.sha256(c), dtype=np.uint8)
+    path = os.path.join(HERE, "hf_bits.npz")
+    np.savez_compressed(path, **out)
+    print("hf_bits.npz: %d bytes; reference soft == AES-NI == oracle == rule on every bitmap" % os.path.getsize(path))
+
+
 def main():
     if sys.argv[1:] == ["br_ref"]:
         return make_br_ref()
+    if sys.argv[1:] == ["hf_bits"]:
+        return make_hf_bits()
     make_br_ref()
+    make_hf_bits()
     make_ref_random()
     kat = make_kat()
     with open(os.path.join(HERE, "kat.json"), "w") as f:

@@ -244,7 +244,9 @@ def random_cases(seed=7):
     """The inputs of the random comparison with the reference build (tests/test_oracle.py; their
     reference results are recorded in tests/golden/ref_random.npz by make_golden.py): 5000 records
     of random bytes in every field, garbage headers and flags included, a random CMAC key and one
-    random message per length of RANDOM_CMAC_LENS.  Returns (records, key, messages)."""
+    random message per length of RANDOM_CMAC_LENS.  A random MAC never matches, so these records
+    exercise the failing side only; passing records with garbage flags, IFIDs of 0 and above 255
+    are the corpus of tests/hf_bits.py (tests/test_hf_bits.py).  Returns (records, key, messages)."""
     rng = np.random.default_rng(seed)
     recs = rng.integers(0, 256, size=(5000, 64), dtype=np.uint8)
     key = rng.integers(0, 256, 16, dtype=np.uint8).tobytes()
