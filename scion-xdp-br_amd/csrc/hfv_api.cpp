@@ -286,6 +286,13 @@ static bool own_stream(const hfv_ctx *ctx, hipStream_t st);
 #ifndef HFV_PUB_FENCE
 #define HFV_PUB_FENCE 1
 #endif
+// HFV_READER_FENCE=0 drops the other half: a publish overwrites a device table without waiting for
+// the launches that still read it (neither the per-stream events nor the overflow synchronize).
+// `make noreaderfence` builds it so that tests/test_gpu_key_publish.py can be shown to fail
+// without the fence; never a product build.
+#ifndef HFV_READER_FENCE
+#define HFV_READER_FENCE 1
+#endif
 
 // Test hooks.  They change what the library does (delays, launch shapes) and exist only in the
 // test build, lib/libscionhfv_test.so (make: -DHFV_TEST_HOOKS); the product library has none of
@@ -380,7 +387,9 @@ static int publish_keys(hfv_ctx *ctx, hipStream_t st, DevState **out)
         memcpy(ctx->host_img->keys.valid, ctx->valid, sizeof ctx->valid);
         ctx->host_img->br = ctx->br;
         // the device table may only be overwritten after every launch that read it completed
-        if (ctx->readers_overflow[next]) {
+        if (!HFV_READER_FENCE) {
+            // A/B build only: no write-after-read fence
+        } else if (ctx->readers_overflow[next]) {
             HIP_TRY(hipDeviceSynchronize());
         } else {
             // the events were recorded after each reader's last launch with the table, so the

@@ -5,6 +5,7 @@ import os
 import numpy as np
 import pytest
 
+import key_tables as KT
 import orc
 import scion_hfv as hfv
 
@@ -135,8 +136,33 @@ def test_key_remove_add_fail_closed(ctx):
     assert np.array_equal(bits_np(bits, n), g["pass_bits"])
 
 
-def test_key_update_is_stream_ordered(ctx):
+def ifid_corpus(ctx):
+    """KEYSEL_IFID and the three-table corpus (tests/key_tables.py) on the device: under KEYSEL_ZERO
+    the verify kernels take slot 0's key from their kernel arguments and never read the device
+    table, so the keysel 1 legs of the key-change tests are the ones that read what was published."""
+    ctx.set_keysel(hfv.KEYSEL_IFID)
+    return dev(KT.corpus()[0]), KT.N, KT.want()
+
+
+def install_table(ctx, name):
+    install(ctx, KT.tables()[name][0])
+
+
+@pytest.mark.parametrize("keysel", [0, 1])
+def test_key_update_is_stream_ordered(ctx, keysel):
     """Batches enqueued before a key change keep the old table (RCU-like)."""
+    if keysel:
+        d, n, want = ifid_corpus(ctx)
+        s = torch.cuda.Stream()
+        outs = [new_bits(n) for _ in range(3)]
+        torch.cuda.synchronize()
+        for o, name in zip(outs, "ABA"):
+            install_table(ctx, name)
+            ctx.verify_records(d, n, o, stream=s)
+        s.synchronize()
+        for o, name in zip(outs, "ABA"):
+            assert np.array_equal(bits_np(o, n), want[name]), name
+        return
     g = orc.load_golden("hf_single.npz")
     n = len(g["records"])
     d = dev(g["records"])
@@ -155,11 +181,33 @@ def test_key_update_is_stream_ordered(ctx):
     assert np.array_equal(bits_np(outs[2], n), g["pass_bits"])
 
 
-def test_key_publish_visible_on_other_streams(ctx):
+@pytest.mark.parametrize("keysel", [0, 1])
+def test_key_publish_visible_on_other_streams(ctx, keysel):
     """A table published by a launch on stream A, its copy queued behind earlier work on A, is
     the table a launch on stream B then reads: B waits for A's publish copy.  Round 2 had no
     such fence; the config-5 loop published on its chunk-0 stream and its chunk-1 kernel, on a
     second stream, could read the previous table (loop parity failure)."""
+    if keysel:
+        d, n, want = ifid_corpus(ctx)
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        scratch = new_bits(n)
+        for wrong in "BC":           # both device tables hold a table that fails A's records
+            install_table(ctx, wrong)
+            ctx.verify_records(d, n, scratch, stream=a)
+            torch.cuda.synchronize()
+            assert np.array_equal(bits_np(scratch, n), want[wrong])
+        install_table(ctx, "A")
+        outs = [new_bits(n) for _ in range(3)]
+        torch.cuda.synchronize()
+        with torch.cuda.stream(a):
+            torch.cuda._sleep(20_000_000)
+        ctx.verify_records(d, n, outs[0], stream=a)
+        ctx.verify_records(d, n, outs[1], stream=b)
+        ctx.verify_records(d, n, outs[2], stream=0)
+        torch.cuda.synchronize()
+        for o in outs:
+            assert np.array_equal(bits_np(o, n), want["A"])
+        return
     g = orc.load_golden("hf_single.npz")
     n = len(g["records"])
     d = dev(g["records"])
@@ -388,10 +436,28 @@ def test_pinned_keymap_attach(ctx, tmp_path, monkeypatch):
     assert np.array_equal(bits_np(bits, n), g["pass_bits"])
 
 
-def test_table_update_after_reader_stream_destroyed(ctx):
+@pytest.mark.parametrize("keysel", [0, 1])
+def test_table_update_after_reader_stream_destroyed(ctx, keysel):
     """A key update after the stream that last read the key table was destroyed: the publish
     fences on an event recorded after that stream's launch, never on the dead stream."""
     import gc
+    if keysel:
+        d, n, want = ifid_corpus(ctx)
+        for name in "ABC":
+            install_table(ctx, name)     # dirty: the next launch publishes a new table
+            s = torch.cuda.Stream()
+            bits = new_bits(n)
+            ctx.verify_records(d, n, bits, stream=s)
+            s.synchronize()
+            assert np.array_equal(bits_np(bits, n), want[name]), name
+            del s
+            gc.collect()
+        install_table(ctx, "A")
+        bits = new_bits(n)
+        ctx.verify_records(d, n, bits, stream=torch.cuda.Stream())
+        torch.cuda.synchronize()
+        assert np.array_equal(bits_np(bits, n), want["A"])
+        return
     raw = orc.KEY_1111
     hk, valid = orc.key_table(raw)
     ctx.key_add(0, raw)

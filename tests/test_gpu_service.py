@@ -9,6 +9,7 @@ import time
 import numpy as np
 import pytest
 
+import key_tables as KT
 import orc
 import scion_hfv as hfv
 from conftest import rerun_on_test_build
@@ -134,9 +135,29 @@ def test_service_sees_rewritten_records(ctx):
     assert np.array_equal(bits_np(bits, n), orc.verify_records(b, hk, valid, 0))
 
 
-def test_service_key_change_is_a_batch_boundary(ctx):
+@pytest.mark.parametrize("keysel", [0, 1])
+def test_service_key_change_is_a_batch_boundary(ctx, keysel):
     """Key add/remove while the service runs apply from the next submitted batch on; the
-    batches posted before keep the old table."""
+    batches posted before keep the old table.  keysel 1: whole 256-key tables change (the three-table
+    corpus of tests/key_tables.py), which the service kernel reads from the device table; slot 0's
+    key alone travels in its kernel arguments."""
+    if keysel:
+        ctx.set_keysel(hfv.KEYSEL_IFID)
+        n = KT.N
+        d = dev(KT.corpus()[0])
+        outs = [new_bits(n, fill=-1) for _ in range(3)]
+        torch.cuda.synchronize()
+        tickets = []
+        for o, name in zip(outs, "ABA"):
+            raw = KT.tables()[name][0]
+            for k in range(256):
+                ctx.key_add(k, raw[16 * k:16 * k + 16])
+            tickets.append(ctx.service_submit(d, n, o))
+        for t in tickets:
+            ctx.service_wait(t, 20000)
+        for o, name in zip(outs, "ABA"):
+            assert np.array_equal(bits_np(o, n), KT.want()[name]), name
+        return
     g = orc.load_golden("hf_single.npz")
     n = len(g["records"])
     d = dev(g["records"])
