@@ -1,6 +1,6 @@
 // hfv_config.cpp -- br-loader's configuration path for C callers: the router's TOML file and
-// the SCION topology.json it names -> the router tables of hfv_br_process (struct
-// hfv_br_config), and the pinned copy of those tables that `hfv-loader attach` publishes.
+// the SCION topology.json it names -> the router tables of hfv_br_process (struct hfv_br_config),
+// their pinned copy that `hfv-loader attach` publishes, their kernel form (compile_br_config).
 //
 // Follows, with the same inputs, checks and messages:
 //   loadConfig / parseTopology / parseInternalIfaces / parseUdpEp / getIfAddr
@@ -854,6 +854,108 @@ int brcfg_open_ro(const char *path, const void **mapping)
 void brcfg_close(const void *mapping)
 {
     if (mapping) munmap((void *)mapping, sizeof(BrcfgFile));
+}
+
+// ---- router tables as the kernel reads them (hfv_br_set_config, a republished pinned config) ----
+static uint32_t le32(const uint8_t *q) { return (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16 | (uint32_t)q[3] << 24; }
+static uint32_t be32(const uint8_t *q) { return (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | (uint32_t)q[3]; }
+static uint32_t le16(const uint8_t *q) { return (uint32_t)q[0] | (uint32_t)q[1] << 8; }
+
+void compile_br_config(const hfv_br_config *in, DevBrConfig *out)
+{
+    memset(out, 0, sizeof *out);
+    out->n_int = in->n_int_ifaces;
+    out->n_ing = in->n_ingress;
+    out->n_egr = in->n_egress;
+    out->n_routes = in->n_routes;
+    for (uint32_t i = 0; i < in->n_int_ifaces; ++i) {
+        const hfv_br_int_iface &a = in->int_ifaces[i];
+        DevBrIntIface &d = out->int_ifaces[i];
+        d.ifindex = a.ifindex;
+        d.family = a.family;
+        for (int w = 0; w < 4; ++w) d.addr[w] = le32(a.addr + 4 * w);
+        d.port = le16(a.port);
+    }
+    for (uint32_t i = 0; i < in->n_ingress; ++i) {   // struct ingress_addr key layout, common.h:73-84
+        const hfv_br_ingress &a = in->ingress[i];
+        DevBrIngress &d = out->ingress[i];
+        if (a.family == HFV_AF_INET) d.v4 = le32(a.addr);
+        else
+            for (int w = 0; w < 4; ++w) d.v6[w] = le32(a.addr + 4 * w);
+        d.port = le16(a.port);
+        d.ifindex16 = a.ifindex & 0xffffu;
+        d.ifid = a.ifid;
+    }
+    for (uint32_t i = 0; i < in->n_egress; ++i) {
+        const hfv_br_egress &a = in->egress[i];
+        DevBrEgress &d = out->egress[i];
+        d.ifid = a.ifid;
+        d.fwd_external = a.fwd_external;
+        d.family = a.family;
+        for (int w = 0; w < 4; ++w) {
+            d.remote[w] = le32(a.remote + 4 * w);
+            d.local[w] = le32(a.local + 4 * w);
+        }
+        d.remote_port = le16(a.remote_port);
+        d.local_port = le16(a.local_port);
+    }
+    for (uint32_t i = 0; i < in->n_routes; ++i) {
+        const hfv_br_route &a = in->routes[i];
+        DevBrRoute &d = out->routes[i];
+        uint32_t width = a.family == HFV_AF_INET ? 32 : a.family == HFV_AF_INET6 ? 128 : 0;
+        d.family = (width && a.prefix_len <= width) ? a.family : 0;
+        d.plen = a.prefix_len;
+        for (int w = 0; w < 4; ++w) {
+            uint32_t lo = 32u * (uint32_t)w, bits = a.prefix_len > lo ? a.prefix_len - lo : 0;
+            d.mask[w] = bits >= 32 ? 0xffffffffu : bits ? ~0u << (32 - bits) : 0u;
+            d.pfx[w] = be32(a.prefix + 4 * w) & d.mask[w];
+        }
+        d.ret = a.ret;
+        d.ifindex = a.ifindex;
+        d.dmac_lo = le32(a.dmac);
+        d.dmac_hi = le16(a.dmac + 4);
+        d.smac_lo = le32(a.smac);
+        d.smac_hi = le16(a.smac + 4);
+    }
+    for (uint32_t i = 0; i < in->n_tx_ports; ++i)
+        if (in->tx_ports[i] < HFV_BR_MAX_TXPORTS) out->tx_bits[in->tx_ports[i] >> 5] |= 1u << (in->tx_ports[i] & 31);
+    memset(out->int_of_ifindex, 0xff, sizeof out->int_of_ifindex);
+    memset(out->egr_of_ifid, 0xff, sizeof out->egr_of_ifid);
+    for (uint32_t i = out->n_int; i-- > 0;)   // reverse: the first match wins
+        if (out->int_ifaces[i].ifindex < 64) out->int_of_ifindex[out->int_ifaces[i].ifindex] = (int8_t)i;
+    for (uint32_t i = out->n_egr; i-- > 0;)
+        if (out->egress[i].ifid < 256) out->egr_of_ifid[out->egress[i].ifid] = (int8_t)i;
+    memset(out->ing_of_ifindex, 0xff, sizeof out->ing_of_ifindex);
+    for (uint32_t i = 0; i < out->n_ing; ++i) {
+        const uint32_t x = out->ingress[i].ifindex16;
+        if (x < 64) out->ing_of_ifindex[x] = out->ing_of_ifindex[x] == -1 ? (int8_t)i : (int8_t)-2;
+    }
+    // egress entries: the route to the link's remote (fib_lookup_as_egress / fib_lookup_egress_br
+    // look up the entry's own remote address, fib_lookup.h:29-180) and the sibling's internal
+    // interface, with the kernel's longest-prefix rule (ties keep the first route)
+    for (uint32_t i = 0; i < out->n_egr; ++i) {
+        DevBrEgress &e = out->egress[i];
+        int best = -1;
+        uint32_t best_len = 0;
+        for (uint32_t r = 0; r < out->n_routes; ++r) {
+            const DevBrRoute &rt = out->routes[r];
+            if (rt.family != e.family) continue;
+            uint32_t diff = 0;
+            for (int w = 0; w < 4; ++w) diff |= (__builtin_bswap32(e.remote[w]) ^ rt.pfx[w]) & rt.mask[w];   // big-endian words
+            if (diff == 0 && (best < 0 || rt.plen > best_len)) {
+                best = (int)r;
+                best_len = rt.plen;
+            }
+        }
+        e.route = best;
+        const uint32_t out_if = best >= 0 ? out->routes[best].ifindex : 0;
+        e.sib_iface = -1;
+        for (uint32_t k = 0; k < out->n_int; ++k)
+            if (out->int_ifaces[k].ifindex == out_if) {
+                e.sib_iface = (int)k;
+                break;
+            }
+    }
 }
 
 }  // namespace hfv

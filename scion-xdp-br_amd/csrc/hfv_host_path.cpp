@@ -1,0 +1,553 @@
+// hfv_host_path.cpp -- the entry points that take frames or records in host memory
+// (hfv_br_process_host, hfv_verify_records_host, hfv_host_register), their staging workers
+// (host thread pool, NUMA pinning), and the router stage of in-library pipelines (hfv_loop.cpp).
+#include <pthread.h>
+#include <stdlib.h>
+
+#include <condition_variable>
+#include <functional>
+#include <mutex>
+#include <thread>
+
+#include "hfv_ctx.h"
+
+// Compact staging record of the host path: INF (8 B) at 0, HF (12 B) at 8, 4 B pad.
+static constexpr size_t kHostRec = 24;
+
+// Host threads for staging copies: HFV_HOST_THREADS, default min(8, cores).
+static int host_threads()
+{
+    static const int t = [] {
+        const char *e = getenv("HFV_HOST_THREADS");
+        int v = e ? atoi(e) : 0;
+        if (v <= 0) {
+            unsigned hc = std::thread::hardware_concurrency();
+            v = hc ? (int)(hc < 8 ? hc : 8) : 4;
+        }
+        return v;
+    }();
+    return t;
+}
+
+// NUMA placement of the host-side workers: the staging copies of a GPU's host path run on
+// the CPUs of the NUMA node its PCIe root port hangs off (one process per GPU, so the
+// first ctx of the process decides).  HFV_NUMA_PIN=0 leaves the threads unpinned.
+static std::mutex g_numa_m;
+static cpu_set_t g_numa_cpus;
+static bool g_numa_set = false;
+
+static void pin_to_numa()
+{
+    std::lock_guard<std::mutex> g(g_numa_m);
+    if (g_numa_set) (void)pthread_setaffinity_np(pthread_self(), sizeof g_numa_cpus, &g_numa_cpus);
+}
+
+// NUMA node of `device` (from its PCI bus id in sysfs) and that node's CPUs that this
+// process may run on; -1 if unknown.
+int device_numa(int device, cpu_set_t *cpus)
+{
+    char bus[64] = {0}, path[256];
+    if (hipDeviceGetPCIBusId(bus, sizeof bus, device) != hipSuccess) return -1;
+    for (char *p = bus; *p; ++p)
+        if (*p >= 'A' && *p <= 'F') *p = (char)(*p - 'A' + 'a');
+    snprintf(path, sizeof path, "/sys/bus/pci/devices/%s/numa_node", bus);
+    FILE *f = fopen(path, "r");
+    if (!f) return -1;
+    int node = -1;
+    if (fscanf(f, "%d", &node) != 1) node = -1;
+    fclose(f);
+    if (node < 0 || !cpus) return node;
+    snprintf(path, sizeof path, "/sys/devices/system/node/node%d/cpulist", node);
+    f = fopen(path, "r");
+    if (!f) return node;
+    cpu_set_t allowed;
+    CPU_ZERO(cpus);
+    if (sched_getaffinity(0, sizeof allowed, &allowed) != 0) CPU_ZERO(&allowed);
+    int a, b;
+    char sep;
+    while (fscanf(f, "%d", &a) == 1) {
+        b = a;
+        if (fscanf(f, "%c", &sep) == 1 && sep == '-') {
+            if (fscanf(f, "%d", &b) != 1) break;
+            if (fscanf(f, "%c", &sep) != 1) sep = 0;
+        }
+        for (int c = a; c <= b && c < CPU_SETSIZE; ++c)
+            if (CPU_ISSET(c, &allowed)) CPU_SET(c, cpus);
+        if (sep != ',') break;
+    }
+    fclose(f);
+    return node;
+}
+
+void note_numa(int device)
+{
+    const char *e = getenv("HFV_NUMA_PIN");
+    if (e && atoi(e) == 0) return;
+    cpu_set_t cpus;
+    int node = device_numa(device, &cpus);
+    std::lock_guard<std::mutex> g(g_numa_m);
+    if (node >= 0 && !g_numa_set && CPU_COUNT(&cpus) > 0) {
+        g_numa_cpus = cpus;
+        g_numa_set = true;
+    }
+}
+
+// Persistent host worker threads for the staging copies (spawning threads per copy cost more
+// than the copies: 32 spawns per 2^20-frame router batch).  Part 0 of every job runs on the
+// calling thread, parts 1..nt-1 on the workers.  Jobs come from one ctx thread at a time.
+class HostPool {
+  public:
+    explicit HostPool(int nt) : nt_(nt)
+    {
+        for (int k = 1; k < nt_; ++k) th_.emplace_back([this, k] {
+            pin_to_numa();
+            work(k);
+        });
+    }
+    ~HostPool()
+    {
+        {
+            std::lock_guard<std::mutex> g(m_);
+            stop_ = true;
+        }
+        cv_.notify_all();
+        for (auto &t : th_) t.join();
+    }
+    void run(size_t n, const std::function<void(size_t, size_t)> &fn)
+    {
+        std::unique_lock<std::mutex> lk(job_m_);   // one job at a time
+        {
+            std::lock_guard<std::mutex> g(m_);
+            fn_ = &fn;
+            n_ = n;
+            left_ = nt_ - 1;
+            ++gen_;
+        }
+        cv_.notify_all();
+        fn(0, n / nt_);
+        std::unique_lock<std::mutex> g(m_);
+        done_.wait(g, [this] { return left_ == 0; });
+        fn_ = nullptr;
+    }
+    int threads() const { return nt_; }
+
+  private:
+    void work(int k)
+    {
+        uint64_t seen = 0;
+        for (;;) {
+            const std::function<void(size_t, size_t)> *fn;
+            size_t n;
+            {
+                std::unique_lock<std::mutex> g(m_);
+                cv_.wait(g, [&] { return stop_ || gen_ != seen; });
+                if (stop_) return;
+                seen = gen_;
+                fn = fn_;
+                n = n_;
+            }
+            (*fn)(n * k / nt_, n * (k + 1) / nt_);
+            std::lock_guard<std::mutex> g(m_);
+            if (--left_ == 0) done_.notify_one();
+        }
+    }
+    int nt_;
+    std::vector<std::thread> th_;
+    std::mutex m_, job_m_;
+    std::condition_variable cv_, done_;
+    const std::function<void(size_t, size_t)> *fn_ = nullptr;
+    size_t n_ = 0;
+    int left_ = 0;
+    uint64_t gen_ = 0;
+    bool stop_ = false;
+};
+
+static HostPool &host_pool()
+{
+    static HostPool pool(host_threads());
+    return pool;
+}
+
+// fn(a, b) over [0, n) split into host_threads() contiguous parts (inline below 8192 items).
+template <class F>
+static void parallel_rows(size_t n, F fn)
+{
+    if (host_threads() <= 1 || n < 8192) {
+        fn((size_t)0, n);
+        return;
+    }
+    host_pool().run(n, std::function<void(size_t, size_t)>(fn));
+}
+
+// dst[i] = {INF, HF} of src record i (the verifier's 20 bytes).
+static void gather_hf(uint8_t *dst, const uint8_t *src, size_t stride, uint32_t inf_off, uint32_t hf_off, size_t n)
+{
+    parallel_rows(n, [=](size_t a, size_t b) {
+        for (size_t i = a; i < b; ++i) {
+            const uint8_t *r = src + i * stride;
+            uint8_t *d = dst + i * kHostRec;
+            memcpy(d, r + inf_off, 8);
+            memcpy(d + 8, r + hf_off, 12);
+        }
+    });
+}
+
+// Row copies between frames in their slots and packed windows: dst row i <- src row i.
+static void copy_rows(uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t width, size_t n)
+{
+    parallel_rows(n, [=](size_t a, size_t b) {
+        for (size_t i = a; i < b; ++i) memcpy(dst + i * dpitch, src + i * spitch, width);
+    });
+}
+
+// Windowed host path.  Per chunk of kBrChunk frames, on alternating streams: strided H2D of
+// the windows + metadata, the kernel (stride = window, lengths clamped to the caller's slot),
+// strided D2H of the rewritten windows + results.  Then frames marked HFV_BR_ACTION_RETRY
+// (headers beyond the window) go through again with whole slots.
+static const size_t kBrChunk = (size_t)1 << 16;
+static const size_t kBrStatWords = HFV_BR_STATS_IFINDEX * 2 * HFV_BR_COUNTERS;
+
+// The device verdict counters of one host-path call: allocated on first use, zeroed on `st`.
+static int brh_stats_buffer(hfv_ctx *ctx, hipStream_t st)
+{
+    if (!ctx->brh_dstats) HIP_TRY(hipMalloc((void **)&ctx->brh_dstats, kBrStatWords * 8));
+    HIP_TRY(hipMemsetAsync(ctx->brh_dstats, 0, kBrStatWords * 8, st));
+    return 0;
+}
+
+// ... added to the caller's (nullable) once the call's launches have completed.
+static int brh_add_stats(hfv_ctx *ctx, uint64_t *stats)
+{
+    if (!stats) return 0;
+    uint64_t tmp[kBrStatWords];
+    HIP_TRY(hipMemcpy(tmp, ctx->brh_dstats, sizeof tmp, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < kBrStatWords; ++k) stats[k] += tmp[k];
+    return 0;
+}
+
+static int brh_buffers(hfv_ctx *ctx, size_t window)
+{
+    for (int i = 0; i < 2; ++i) {
+        if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
+        if (!ctx->brh_dio[i]) {
+            HIP_TRY(hipMalloc((void **)&ctx->brh_dio[i], kBrChunk * 12));
+            HIP_TRY(hipHostMalloc((void **)&ctx->brh_hio[i], kBrChunk * 12, hipHostMallocDefault));
+        }
+    }
+    if (ctx->brh_win_cap < window) {
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(hipStreamSynchronize(ctx->hstream[i]));
+            if (ctx->brh_dwin[i]) (void)hipFree(ctx->brh_dwin[i]);
+            if (ctx->brh_hwin[i]) (void)hipHostFree(ctx->brh_hwin[i]);
+            ctx->brh_dwin[i] = ctx->brh_hwin[i] = nullptr;
+            HIP_TRY(hipMalloc((void **)&ctx->brh_dwin[i], kBrChunk * window));
+            HIP_TRY(hipHostMalloc((void **)&ctx->brh_hwin[i], kBrChunk * window, hipHostMallocDefault));
+        }
+        ctx->brh_win_cap = window;
+    }
+    return 0;
+}
+
+// One chunk: frames[k * fstride] for k < cnt (window bytes each), metadata through pinned io.
+static int brh_chunk(hfv_ctx *ctx, int sl, uint8_t *frames, size_t fstride, size_t maxlen, size_t window,
+                     const uint16_t *len, const uint32_t *ifx, size_t cnt)
+{
+    hipStream_t st = ctx->hstream[sl];
+    uint8_t *hio = ctx->brh_hio[sl], *dio = ctx->brh_dio[sl];
+    memcpy(hio, len, cnt * 2);
+    memcpy(hio + kBrChunk * 2, ifx, cnt * 4);
+    HIP_TRY(hipMemcpyAsync(dio, hio, kBrChunk * 6, hipMemcpyHostToDevice, st));
+    // the header windows, packed by host threads into pinned staging, then one linear DMA
+    copy_rows(ctx->brh_hwin[sl], window, frames, fstride, window, cnt);
+    HIP_TRY(hipMemcpyAsync(ctx->brh_dwin[sl], ctx->brh_hwin[sl], cnt * window, hipMemcpyHostToDevice, st));
+    int rc = with_tables(ctx, st, "br_process launch", [&](DevState *ds) {
+        return launch_br_process(br_geom(ctx), ds, ctx->brh_dwin[sl], window, (uint32_t)maxlen, (uint32_t)window,
+                                 (const uint16_t *)dio, (const uint32_t *)(dio + kBrChunk * 2), cnt,
+                                 dio + kBrChunk * 6, dio + kBrChunk * 7, (int32_t *)(dio + kBrChunk * 8),
+                                 ctx->brh_dstats, st);
+    });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->brh_hwin[sl], ctx->brh_dwin[sl], cnt * window, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hio + kBrChunk * 6, dio + kBrChunk * 6, kBrChunk * 6, hipMemcpyDeviceToHost, st));
+    return 0;
+}
+
+// A retired chunk (its stream synchronized): the rewritten windows back into the frames
+// (host threads), and the per-frame results.
+static void brh_results(hfv_ctx *ctx, int sl, uint8_t *frames, size_t fstride, size_t window, size_t cnt,
+                        uint8_t *action, uint8_t *verdict, int32_t *egress)
+{
+    copy_rows(frames, fstride, ctx->brh_hwin[sl], window, window, cnt);
+    const uint8_t *hio = ctx->brh_hio[sl];
+    memcpy(action, hio + kBrChunk * 6, cnt);
+    memcpy(verdict, hio + kBrChunk * 7, cnt);
+    memcpy(egress, hio + kBrChunk * 8, cnt * 4);
+}
+
+uint8_t *host_dev_ptr(hfv_ctx *ctx, const void *p, size_t bytes)
+{
+    const uint8_t *q = (const uint8_t *)p;
+    for (int i = 0; i < ctx->nhreg; ++i) {
+        const hfv_ctx::HostRange &r = ctx->hreg[i];
+        if (q >= r.host && q + bytes <= r.host + r.bytes) return r.dev + (q - r.host);
+    }
+    return nullptr;
+}
+
+// Zero-copy: the frames are in a registered (mapped) ring, so the kernel reads each header
+// window across PCIe itself and writes back only the rewritten rows; no DMA of frame bytes and
+// no retry pass (the whole frame stays addressable).  Per-frame metadata uses the caller's
+// arrays in place when they are registered too, else one copy each way.
+static int br_zero_copy(hfv_ctx *ctx, uint8_t *dframes, size_t slot, const uint16_t *len, const uint32_t *ifx,
+                        size_t n, uint8_t *action, uint8_t *verdict, int32_t *egress, uint64_t *stats)
+{
+    hipStream_t st = ctx->stream;
+    int rc = brh_stats_buffer(ctx, st);
+    if (rc) return rc;
+    uint16_t *dlen = (uint16_t *)host_dev_ptr(ctx, len, n * 2);
+    uint32_t *difx = (uint32_t *)host_dev_ptr(ctx, ifx, n * 4);
+    uint8_t *dact = host_dev_ptr(ctx, action, n), *dver = host_dev_ptr(ctx, verdict, n);
+    int32_t *degr = (int32_t *)host_dev_ptr(ctx, egress, n * 4);
+    size_t need = n * 16;
+    if ((!dlen || !difx || !dact || !dver || !degr) && ctx->zc_cap < need) {
+        if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
+        ctx->zc_meta = nullptr;
+        HIP_TRY(hipMalloc((void **)&ctx->zc_meta, need));
+        ctx->zc_cap = need;
+    }
+    uint8_t *m = ctx->zc_meta;
+    if (!dlen) { dlen = (uint16_t *)m; HIP_TRY(hipMemcpyAsync(dlen, len, n * 2, hipMemcpyHostToDevice, st)); }
+    if (!difx) { difx = (uint32_t *)(m + n * 4); HIP_TRY(hipMemcpyAsync(difx, ifx, n * 4, hipMemcpyHostToDevice, st)); }
+    bool cp_act = !dact, cp_ver = !dver, cp_egr = !degr;
+    if (cp_act) dact = m + n * 2;
+    if (cp_ver) dver = m + n * 3;
+    if (cp_egr) degr = (int32_t *)(m + n * 8);
+    rc = with_tables(ctx, st, "br_process launch", [&](DevState *ds) {
+        return launch_br_process(br_geom(ctx), ds, dframes, slot, (uint32_t)slot, (uint32_t)slot, dlen, difx, n, dact,
+                                 dver, degr, ctx->brh_dstats, st);
+    });
+    if (rc) return rc;
+    if (cp_act) HIP_TRY(hipMemcpyAsync(action, dact, n, hipMemcpyDeviceToHost, st));
+    if (cp_ver) HIP_TRY(hipMemcpyAsync(verdict, dver, n, hipMemcpyDeviceToHost, st));
+    if (cp_egr) HIP_TRY(hipMemcpyAsync(egress, degr, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return brh_add_stats(ctx, stats);
+}
+
+int hfv::br_zc_prepare(hfv_ctx *ctx)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    SVC_QUIESCE(ctx);
+    HIP_TRY(hipSetDevice(ctx->device));
+    return 0;
+}
+
+int hfv::br_dev_launch(hfv_ctx *ctx, void *stream, uint8_t *dframes, size_t slot, const uint16_t *dlen,
+                       const uint32_t *difx, size_t n, uint8_t *dact, uint8_t *dver, int32_t *degr, uint64_t *dstats,
+                       uint8_t *dout)
+{
+    if (n == 0) return 0;
+    return with_tables(ctx, (hipStream_t)stream, "br_process launch", [&](DevState *ds) {
+        return launch_br_process(br_geom(ctx), ds, dframes, slot, (uint32_t)slot, (uint32_t)slot, dlen, difx, n, dact,
+                                 dver, degr, dstats, stream, nullptr, nullptr, dout);
+    });
+}
+
+extern "C" {
+
+int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16_t *len,
+                        const uint32_t *ingress_ifindex, size_t n, size_t window, uint8_t *action,
+                        uint8_t *verdict, int32_t *egress_ifindex, uint64_t *stats)
+{
+    if (n == 0) return ctx ? 0 : fail(-EINVAL, "ctx is NULL");
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (!frames || !len || !ingress_ifindex || !action || !verdict || !egress_ifindex) return fail(-EINVAL, "null buffer");
+    if (slot < 64 || (slot & 7) || slot > 65535 * 8) return fail(-EINVAL, "slot must be >= 64 and a multiple of 8");
+    if (window == 0) window = slot < 256 ? slot : 256;
+    if (window < 64 || (window & 7) || window > slot) return fail(-EINVAL, "window must be a multiple of 8 in [64, slot]");
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    uint8_t *dframes = host_dev_ptr(ctx, frames, n * slot);
+    if (dframes) return br_zero_copy(ctx, dframes, slot, len, ingress_ifindex, n, action, verdict, egress_ifindex, stats);
+    int rc = brh_buffers(ctx, window > slot ? slot : window);
+    if (!rc) rc = brh_stats_buffer(ctx, ctx->hstream[0]);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->hstream[0]));
+    size_t nchunks = (n + kBrChunk - 1) / kBrChunk;
+    size_t first_of[2] = {0, 0}, cnt_of[2] = {0, 0};
+    for (size_t c = 0; c < nchunks + 2; ++c) {
+        int sl = (int)(c & 1);
+        if (c >= 2) {
+            HIP_TRY(hipStreamSynchronize(ctx->hstream[sl]));
+            size_t f = first_of[sl];
+            brh_results(ctx, sl, frames + f * slot, slot, window, cnt_of[sl], action + f, verdict + f,
+                        egress_ifindex + f);
+        }
+        if (c >= nchunks) continue;
+        size_t first = c * kBrChunk, cnt = n - first < kBrChunk ? n - first : kBrChunk;
+        rc = brh_chunk(ctx, sl, frames + first * slot, slot, slot, window, len + first, ingress_ifindex + first, cnt);
+        if (rc) return rc;
+        first_of[sl] = first;
+        cnt_of[sl] = cnt;
+    }
+    // frames whose headers did not fit the window: whole slots, in chunks, through a bounce buffer
+    size_t nretry = 0;
+    for (size_t i = 0; i < n; ++i) nretry += action[i] == HFV_BR_ACTION_RETRY;
+    if (nretry) {
+        rc = brh_buffers(ctx, slot);
+        if (rc) return rc;
+        uint8_t *bounce = nullptr;
+        size_t cap = nretry < kBrChunk ? nretry : kBrChunk;
+        HIP_TRY(hipHostMalloc((void **)&bounce, cap * slot + cap * 8, hipHostMallocDefault));
+        uint16_t *blen = (uint16_t *)(bounce + cap * slot);
+        uint32_t *bif = (uint32_t *)(bounce + cap * slot + cap * 2);
+        size_t *idx = (size_t *)malloc(cap * sizeof(size_t));
+        size_t i = 0;
+        while (rc == 0 && i < n) {
+            size_t cnt = 0;
+            for (; i < n && cnt < cap; ++i) {
+                if (action[i] != HFV_BR_ACTION_RETRY) continue;
+                memcpy(bounce + cnt * slot, frames + i * slot, slot);
+                blen[cnt] = len[i];
+                bif[cnt] = ingress_ifindex[i];
+                idx[cnt++] = i;
+            }
+            if (!cnt) break;
+            rc = brh_chunk(ctx, 0, bounce, slot, slot, slot, blen, bif, cnt);
+            if (rc == 0 && hipStreamSynchronize(ctx->hstream[0]) != hipSuccess) rc = fail(-EIO, "retry chunk");
+            for (size_t k = 0; rc == 0 && k < cnt; ++k) {
+                size_t j = idx[k];
+                memcpy(frames + j * slot, ctx->brh_hwin[0] + k * slot, slot);
+                action[j] = ctx->brh_hio[0][kBrChunk * 6 + k];
+                verdict[j] = ctx->brh_hio[0][kBrChunk * 7 + k];
+                memcpy(&egress_ifindex[j], ctx->brh_hio[0] + kBrChunk * 8 + 4 * k, 4);
+            }
+        }
+        free(idx);
+        (void)hipHostFree(bounce);
+        if (rc) return rc;
+    }
+    return brh_add_stats(ctx, stats);
+}
+
+int hfv_host_register(hfv_ctx *ctx, void *ptr, size_t bytes)
+{
+    if (!ctx || !ptr || !bytes) return fail(-EINVAL, "bad argument");
+    if (ctx->nhreg == 16) return fail(-ENOMEM, "at most 16 registered host buffers per ctx");
+    DeviceGuard g(ctx->device);
+    HIP_TRY(hipHostRegister(ptr, bytes, hipHostRegisterMapped));
+    void *dev = nullptr;
+    hipError_t e = hipHostGetDevicePointer(&dev, ptr, 0);
+    if (e != hipSuccess) {
+        (void)hipHostUnregister(ptr);
+        return hip_fail(e, "hipHostGetDevicePointer");
+    }
+    ctx->hreg[ctx->nhreg++] = {(uint8_t *)ptr, bytes, (uint8_t *)dev};
+    return 0;
+}
+
+int hfv_host_unregister(hfv_ctx *ctx, void *ptr)
+{
+    if (!ctx || !ptr) return fail(-EINVAL, "bad argument");
+    DeviceGuard g(ctx->device);
+    for (int i = 0; i < ctx->nhreg; ++i) {
+        if (ctx->hreg[i].host != ptr) continue;
+        HIP_TRY(hipDeviceSynchronize());   // no launch may still address it
+        HIP_TRY(hipHostUnregister(ptr));
+        ctx->hreg[i] = ctx->hreg[--ctx->nhreg];
+        return 0;
+    }
+    return fail(-EINVAL, "buffer was not registered with this ctx");
+}
+
+// Zero-copy host batch: the records lie in a registered (mapped) host buffer, so one verify
+// launch reads each record's INF/HF words across PCIe itself (20 of the 64 bytes; no bulk
+// H2D copy).  The bitmap is written in place when it is registered too, else to a device
+// buffer and copied back.
+static int verify_records_zero_copy(hfv_ctx *ctx, const uint8_t *drecs, size_t stride, size_t n, uint64_t *pass_bits)
+{
+    hipStream_t st = ctx->stream;
+    const size_t words = (n + 63) / 64;
+    uint64_t *dbits = (uint64_t *)host_dev_ptr(ctx, pass_bits, words * 8);
+    if (!dbits) {
+        if (ctx->zc_cap < words * 8) {
+            if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
+            ctx->zc_meta = nullptr;
+            ctx->zc_cap = 0;
+            HIP_TRY(hipMalloc((void **)&ctx->zc_meta, words * 8));
+            ctx->zc_cap = words * 8;
+        }
+        dbits = (uint64_t *)ctx->zc_meta;
+    }
+    int rc = with_tables(ctx, st, "verify_records launch (zero-copy)", [&](DevState *ds) {
+        return launch_verify_records(ctx->geom, &ds->keys, &ctx->host_img->keys, ctx->keysel, drecs, stride, n,
+                                     ctx->inf_off, ctx->hf_off, dbits, st, nullptr, nullptr, /*interleaved=*/true);
+    });
+    if (rc) return rc;
+    if (dbits == (uint64_t *)ctx->zc_meta) HIP_TRY(hipMemcpyAsync(pass_bits, dbits, words * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+// Host batch: chunks of records go host -> pinned -> device, verified, bitmap back; two
+// streams alternate so chunk k's copy-in overlaps chunk k-1's kernel and copy-out.  Records
+// in a registered buffer (hfv_host_register) take the zero-copy path instead.
+int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_t n, uint64_t *pass_bits)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    int rc = check_records(ctx, recs, stride, pass_bits);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    if (const uint8_t *drecs = host_dev_ptr(ctx, recs, (n - 1) * stride + ctx->hf_off + 12))
+        return verify_records_zero_copy(ctx, drecs, stride, n, pass_bits);
+    // Staging: each chunk's records are gathered on the host into a compact pinned layout of
+    // kHostRec bytes per record (INF at 0, HF at 8: the 20 bytes the verifier reads), so
+    // PCIe moves 24 B instead of the record stride; the gather is split over host threads
+    // and chunk c's gather overlaps chunk c-1's copy, kernel and copy-back on the other stream.
+    const size_t chunk = (size_t)1 << 18;   // records per chunk
+    if (ctx->host_chunk < chunk * kHostRec) {
+        for (int i = 0; i < 2; ++i) {
+            if (ctx->h_pin[i]) (void)hipHostFree(ctx->h_pin[i]);
+            if (ctx->d_rec[i]) (void)hipFree(ctx->d_rec[i]);
+            if (ctx->h_bits[i]) (void)hipHostFree(ctx->h_bits[i]);
+            if (ctx->d_bits[i]) (void)hipFree(ctx->d_bits[i]);
+            ctx->h_pin[i] = ctx->d_rec[i] = nullptr;
+            ctx->h_bits[i] = ctx->d_bits[i] = nullptr;
+            if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
+            HIP_TRY(hipHostMalloc((void **)&ctx->h_pin[i], chunk * kHostRec, hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&ctx->d_rec[i], chunk * kHostRec));
+            HIP_TRY(hipHostMalloc((void **)&ctx->h_bits[i], chunk / 8, hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&ctx->d_bits[i], chunk / 8));
+        }
+        ctx->host_chunk = chunk * kHostRec;
+    }
+    size_t nchunks = (n + chunk - 1) / chunk;
+    size_t pending_words[2] = {0, 0};
+    size_t pending_first[2] = {0, 0};
+    for (size_t c = 0; c < nchunks + 2; ++c) {
+        int slot = (int)(c & 1);
+        hipStream_t st = ctx->hstream[slot];
+        if (c >= 2) {   // retire chunk c-2 (same slot)
+            HIP_TRY(hipStreamSynchronize(st));
+            memcpy(pass_bits + pending_first[slot], ctx->h_bits[slot], pending_words[slot] * 8);
+        }
+        if (c >= nchunks) continue;
+        size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
+        gather_hf(ctx->h_pin[slot], (const uint8_t *)recs + first * stride, stride, ctx->inf_off, ctx->hf_off, cnt);
+        HIP_TRY(hipMemcpyAsync(ctx->d_rec[slot], ctx->h_pin[slot], cnt * kHostRec, hipMemcpyHostToDevice, st));
+        rc = with_tables(ctx, st, "verify_records launch", [&](DevState *ds) {
+            return launch_verify_records(ctx->geom, &ds->keys, &ctx->host_img->keys, ctx->keysel, ctx->d_rec[slot],
+                                         kHostRec, cnt, 0, 8, ctx->d_bits[slot], st);
+        });
+        if (rc) return rc;
+        size_t words = (cnt + 63) / 64;
+        HIP_TRY(hipMemcpyAsync(ctx->h_bits[slot], ctx->d_bits[slot], words * 8, hipMemcpyDeviceToHost, st));
+        pending_words[slot] = words;
+        pending_first[slot] = first / 64;
+    }
+    return 0;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
-// hfv_internal.h -- shared between the host API (hfv_api.cpp, hfv_aes_host.cpp) and the
-// kernel launchers (hfv_kernels.hip).  Not installed.
+// hfv_internal.h -- shared between the host code (the units around hfv_ctx.h, hfv_aes_host.cpp)
+// and the kernel launchers (hfv_kernels.hip).  Not installed.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -181,13 +181,17 @@ struct LaunchGeom {
 // contiguous tile range per block -- for records in host memory, where the 256 ranges far
 // apart thrash the GPU's translation of 4 KiB host pages (zero-copy 2^20: 1.60 -> 1.27 ms)
 // One-launch-per-batch record verify: the slot-0 key rows and T0 travel in the kernel arguments
-// too (RecArgs), so a block's prologue is one memory hop (SvcArgs has the same fields).
+// too, so a block's prologue is one memory hop (the kernarg segment) instead of two (kernarg ->
+// key table / table image).  BatchArgs and SvcArgs embed the same prologue.  The struct keeps the
+// name the k_verify_records symbols carry; KeyPrologue is what it is called where it is embedded.
 struct RecArgs {
-    uint32_t key0[kDevKeyRows * 4];
+    uint32_t key0[kDevKeyRows * 4];   // the slot-0 device key rows (KEYSEL_ZERO)
     uint32_t key0_ok, pad_[3];
     uint32_t t0[256];
 };
-// host_keys: the key table as last published (the host staging image), for RecArgs
+using KeyPrologue = RecArgs;
+// host_keys: the key table as last published (the host staging image; null: no slot-0 key)
+__attribute__((visibility("hidden"))) KeyPrologue key_prologue(const DevKeyTable *host_keys);
 int launch_verify_records(const LaunchGeom &g, const DevKeyTable *tab, const DevKeyTable *host_keys, int keysel,
                           const uint8_t *recs,
                           size_t stride, size_t n, uint32_t inf_off, uint32_t hf_off, uint64_t *bits,
@@ -249,14 +253,14 @@ struct SvcArgs {
     uint32_t relay_delay_us;  // test hook (hfv_debug_relay_delay): the relay spins this long after each host read
     uint32_t launch;          // grid number (SvcArea parity)
     uint32_t pad_[3];
-    // What every block reads before its first tile, in the kernel arguments so that the block
-    // prologue is one memory hop (the kernarg segment) instead of two (kernarg -> key table /
-    // table image): the slot-0 device key rows (KEYSEL_ZERO, as published for this grid) and T0.
-    uint32_t key0[kDevKeyRows * 4];
-    uint32_t key0_ok, pad2_[3];
-    uint32_t t0[256];
+    KeyPrologue pro;   // what every block reads before its first tile (slot 0 as published for this grid)
     SvcDescLite inl[kSvcInline];
 };
+// the kernels read the prologue at the byte offsets it had as three separate fields
+static_assert(sizeof(KeyPrologue) == 1232 && offsetof(KeyPrologue, key0_ok) == 192 && offsetof(KeyPrologue, t0) == 208,
+              "KeyPrologue layout");
+static_assert(offsetof(SvcArgs, pro) == 120 && offsetof(SvcArgs, inl) == 1352 && sizeof(SvcArgs) == 3400,
+              "SvcArgs layout");
 // both travel as one by-value kernel argument: the kernarg segment holds at most 4 KiB
 static_assert(sizeof(SvcArgs) <= 4096, "SvcArgs exceeds the 4 KiB kernel-argument segment");
 static_assert(sizeof(RecArgs) + 128 <= 4096, "RecArgs and the launch's other arguments exceed 4 KiB");
@@ -276,12 +280,13 @@ struct BatchArgs {
     // (wave 0); [4 + k] block k's s_memrealtime at its entry, [4 + kBatchStampBlocks + k] when its
     // last wave left (atomic max: the host zeroes it before a timed launch)
     uint64_t *clk;
-    uint32_t key0[kDevKeyRows * 4];
-    uint32_t key0_ok, pad_[3];
-    uint32_t t0[256];
+    KeyPrologue pro;
     SvcDescLite d[kBatchMax];
     uint32_t cum[kBatchMax + 1];
 };
+static_assert(offsetof(BatchArgs, pro) == 32 && offsetof(BatchArgs, d) == 1264 && offsetof(BatchArgs, cum) == 3312 &&
+                  sizeof(BatchArgs) == 3576,
+              "BatchArgs layout");
 static_assert(sizeof(BatchArgs) <= 4096, "BatchArgs exceeds the 4 KiB kernel-argument segment");
 int launch_verify_batches(const LaunchGeom &g, int keysel, const BatchArgs &args, void *stream, void *ev_start,
                           void *ev_stop);

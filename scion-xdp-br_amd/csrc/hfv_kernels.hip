@@ -310,7 +310,7 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
     if (b1 == b0) return;   // (the launcher gives every block at least one tile)
     const uint32_t last = b1 - 1;
     const uint32_t inf_off = a->inf_off, hf_off = a->hf_off;
-    UniformKey ukey(a->key0, a->key0_ok);
+    UniformKey ukey(a->pro.key0, a->pro.key0_ok);
     // diagnostics, stored before the first record loads are issued (a store issued after them would
     // make the loop's first reuse of its data registers wait for every load ahead of it: vmcnt(0))
     if (threadIdx.x == 0 && a->clk) {
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
         batch_map(a, at(gg[d]), bt[d]);
         buf[d] = batch_load(bt[d], at(gg[d]), lane, inf_off, hf_off);
     }
-    fill_block<KEYSEL>(a->t0, a->tab, kBlock);
+    fill_block<KEYSEL>(a->pro.t0, a->tab, kBlock);
     __syncthreads();
     const Lane l = lane_bases();
     // verdict words wait in a per-wave stash (lane k: the wave's k-th tile, with its own bitmap
@@ -899,7 +899,7 @@ __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
     (void)args;
     const uint32_t lane = threadIdx.x & 63;
     SvcDev *dev = a->dev;
-    UniformKey ukey(a->key0, a->key0_ok);
+    UniformKey ukey(a->pro.key0, a->pro.key0_ok);
     const uint32_t inf_off = a->inf_off, hf_off = a->hf_off;
     if (threadIdx.x == 0) {
         s_svc_next = 0;
@@ -917,7 +917,7 @@ __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
     // starts relaying right after it.
     const uint32_t nthr = blockIdx.x == 0 ? 1024 - 64 : 1024;   // threads filling the tables
     const bool relay = blockIdx.x == 0 && threadIdx.x >= nthr;
-    fill_block<KEYSEL>(a->t0, a->tab, nthr);
+    fill_block<KEYSEL>(a->pro.t0, a->tab, nthr);
     __syncthreads();
     if (threadIdx.x == 0) {
         dev->blk_start[blockIdx.x] = memrealtime();
@@ -1249,9 +1249,12 @@ static inline unsigned grid_for(uint64_t n, int block, int num_cus, int per_cu)
     return (unsigned)(blocks ? blocks : 1);
 }
 
-static RecArgs rec_args(const DevKeyTable *host_keys)
+// The argument prologue of the verify kernels (RecArgs, BatchArgs::pro, SvcArgs::pro): slot 0's
+// device key rows and valid bit from the key table as last published (null: no key, so every
+// KEYSEL_ZERO record fails), and T0.
+KeyPrologue key_prologue(const DevKeyTable *host_keys)
 {
-    RecArgs ka;
+    KeyPrologue ka;
     memset(&ka, 0, sizeof ka);
     if (host_keys) {
         for (int r = 0; r < kDevKeyRows; ++r) memcpy(&ka.key0[4 * r], host_keys->rows[r][0], 16);
@@ -1279,10 +1282,7 @@ int launch_verify_records(const LaunchGeom &g, const DevKeyTable *tab, const Dev
         a.cum[0] = 0;
         a.cum[1] = a.total;
         a.d[0] = {(uint64_t)(uintptr_t)recs, (uint64_t)(uintptr_t)bits, (uint64_t)n, (uint64_t)stride};
-        const RecArgs ra = rec_args(host_keys);
-        memcpy(a.key0, ra.key0, sizeof a.key0);
-        a.key0_ok = ra.key0_ok;
-        memcpy(a.t0, ra.t0, sizeof a.t0);
+        a.pro = key_prologue(host_keys);
         return launch_verify_batches(g, keysel, a, stream, ev_start, ev_stop);
     }
     using K = void (*)(const DevKeyTable *, const uint8_t *, uint64_t, uint64_t, uint32_t, uint32_t, uint64_t *,
@@ -1293,7 +1293,7 @@ int launch_verify_records(const LaunchGeom &g, const DevKeyTable *tab, const Dev
     const unsigned grid = grid_for(n, kBlock, g.num_cus, 1);
     hipExtLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, (hipEvent_t)ev_start,
                           (hipEvent_t)ev_stop, 0u, tab, recs, (uint64_t)stride, (uint64_t)n, inf_off, hf_off, bits,
-                          (uint64_t *)nullptr, rec_args(host_keys));
+                          (uint64_t *)nullptr, key_prologue(host_keys));
     return (int)hipGetLastError();
 }
 
@@ -1303,7 +1303,7 @@ int launch_verify_stamped(const LaunchGeom &g, const DevKeyTable *tab, const Dev
     const unsigned grid = grid_for(n, kBlock, g.num_cus, 1);
     hipLaunchKernelGGL((k_verify_records<HFV_KEYSEL_ZERO, 1, 1>), dim3(grid), dim3(kBlock), 0, (hipStream_t)stream, tab,
                        recs, (uint64_t)64, (uint64_t)n, (uint32_t)HFV_REC_INF_OFF, (uint32_t)HFV_REC_HF_OFF, bits,
-                       stamps, rec_args(host_keys));
+                       stamps, key_prologue(host_keys));
     return (int)hipGetLastError();
 }
 

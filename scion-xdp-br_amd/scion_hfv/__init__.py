@@ -738,7 +738,7 @@ class Ctx:
 
     def service_weights(self):
         """Diagnostic: the block weights the next service grid will use (per XCD 0..7, then
-        block 0's), in 1/1024 of an equal share (svc_balance, hfv_api.cpp)."""
+        block 0's), in 1/1024 of an equal share (svc_balance, hfv_service.cpp)."""
         w = (ctypes.c_uint32 * 9)()
         L = lib()
         L.hfv_debug_service_weights.argtypes = [ctypes.c_void_p, ctypes.c_void_p]

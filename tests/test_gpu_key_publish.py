@@ -1,4 +1,4 @@
-"""Key-table publication (publish_keys / note_reader in csrc/hfv_api.cpp) held on the kernels that
+"""Key-table publication (publish_keys / note_reader in csrc/hfv_publish.cpp) held on the kernels that
 read the device table: a launch verifies under the table it was launched with, whatever the host
 installs afterwards and on whichever stream.
 

@@ -245,7 +245,7 @@ def test_service_run_async(ctx, count):
 
 
 def test_service_balance_weights_stay_bounded(ctx):
-    """svc_balance (hfv_api.cpp) re-derives the per-XCD block weights after every run grid:
+    """svc_balance (hfv_service.cpp) re-derives the per-XCD block weights after every run grid:
     over a dozen K = 20 grids of 2^20 records (the bench's shape) they stay inside the clamp
     [1/2, 2] of an equal share, and every grid's verdicts stay equal
     to the launch path's whatever the shares."""
