@@ -51,6 +51,17 @@
 #include "hfv_aes_dev.h"
 #include "hfv_internal.h"
 
+// HFV_MUT_WINEDGE = 1..7 (`make winedge`): deliberately wrong window-edge cases in the access
+// helpers below (1 rd32, 2 and 7 wr32's HBM and LDS half, 3 in_ext, 4 beyond, 6 rd16; 5 is
+// FrameReader::u32 in hfv_frames_kernel.hip), each using or storing another in-bounds value or
+// leaving a store out, for the libraries tests/test_gpu_br_shift.py must fail on.  (Not 2: the only
+// wr32 at a variable offset is PathMeta, of which the router changes byte 0 alone, so the half
+// past the window always re-stores bytes as they were read; 7 drops the half that changes.)
+// 0 (the default, every product build): none of them.
+#ifndef HFV_MUT_WINEDGE
+#define HFV_MUT_WINEDGE 0
+#endif
+
 namespace hfv {
 
 static __shared__ DevBrConfig s_br;
@@ -197,11 +208,12 @@ constexpr int kBrExt = 8;
 // the 32 bits starting at byte b (0 <= b <= 4, or b <= 6 for the low 16) of the frame's ext bytes
 __device__ __forceinline__ uint32_t ext_u32(const BrFrame &k, int b)
 {
+    if (HFV_MUT_WINEDGE == 3 && b > 6) b = 6;   // the mutant's two extra bytes: clamped into the registers
     return __builtin_amdgcn_alignbyte(k.ext[1], b < 4 ? k.ext[0] : k.ext[1], (uint32_t)b & 3u);
 }
 __device__ __forceinline__ bool in_ext(const BrFrame &k, int off, int size)
 {
-    return HFV_BR_EXT && k.has_ext && off >= k.win && off + size <= k.win + kBrExt;
+    return HFV_BR_EXT && k.has_ext && off >= k.win && off + size <= k.win + kBrExt + (HFV_MUT_WINEDGE == 3 ? 2 : 0);
 }
 __device__ __forceinline__ uint32_t rd8(const BrFrame &k, int off)
 {
@@ -230,7 +242,7 @@ __device__ __forceinline__ uint32_t lds_u16_at(const BrFrame &k, int off)
 __device__ __forceinline__ uint32_t rd16(const BrFrame &k, int off)
 {
     if (k.win == 0) return g16(k.p + off);
-    const bool in = (uint32_t)off + 2 <= (uint32_t)k.win;
+    const bool in = (uint32_t)off + 2 <= (uint32_t)k.win + (HFV_MUT_WINEDGE == 6 ? 2u : 0u);   // mutant: the pad dword
     uint32_t v = lds_u16_at(k, in ? off : 0);
     if (!in) {
         if (in_ext(k, off, 2)) {
@@ -245,7 +257,8 @@ __device__ __forceinline__ uint32_t rd16(const BrFrame &k, int off)
 __device__ __forceinline__ uint32_t rd32(const BrFrame &k, int off)
 {
     if (k.win == 0) return g32(k.p + off);
-    const bool in = (uint32_t)off + 4 <= (uint32_t)k.win;
+    // (mutant 1: a field across the window end is read from the row and its pad dword)
+    const bool in = (uint32_t)off + 4 <= (uint32_t)k.win || (HFV_MUT_WINEDGE == 1 && (uint32_t)off < (uint32_t)k.win);
     uint32_t v = lds_u32_at(k, in ? off : 0);
     if (!in) {
         if (in_ext(k, off, 4)) {
@@ -306,8 +319,8 @@ __device__ __forceinline__ void wr32(BrFrame &k, int off, uint32_t v)
             uint8_t *h = k.po + off;
             h[0] = (uint8_t)v; h[1] = (uint8_t)(v >> 8); h[2] = (uint8_t)(v >> 16); h[3] = (uint8_t)(v >> 24);
         } else {
-            wr16(k, off, v);
-            wr16(k, off + 2, v >> 16);
+            if (HFV_MUT_WINEDGE != 7) wr16(k, off, v);
+            if (!(HFV_MUT_WINEDGE == 2 && off + 2 >= k.win)) wr16(k, off + 2, v >> 16);
         }
     }
 }
@@ -316,7 +329,7 @@ __device__ __forceinline__ void wr32(BrFrame &k, int off, uint32_t v)
 // frame, running past the window marks the frame `cut` (the host path re-runs it whole).
 __device__ __forceinline__ bool beyond(BrFrame &k, int end)
 {
-    if (end <= k.lim) return false;
+    if (HFV_MUT_WINEDGE == 4 ? end < k.lim : end <= k.lim) return false;
     if (end <= k.len) k.cut = true;
     return true;
 }

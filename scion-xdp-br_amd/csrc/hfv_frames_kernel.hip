@@ -38,6 +38,12 @@
 #include "hfv_frame_parse.h"
 #include "hfv_internal.h"
 
+// HFV_MUT_WINEDGE = 5 (`make winedge`, see hfv_br_kernel.hip): u32 takes a field across the window
+// end from the row and its zeroed pad dword.  0 (the default, every product build): as written.
+#ifndef HFV_MUT_WINEDGE
+#define HFV_MUT_WINEDGE 0
+#endif
+
 namespace hfv {
 
 constexpr int kFrWin = 128;              // staged bytes per frame
@@ -67,7 +73,7 @@ struct FrameReader {
     }
     __device__ __forceinline__ uint32_t u32(int off) const
     {
-        if (WIN == 0 || off + 4 > WIN) return g16(off) | g16(off + 2) << 16;
+        if (WIN == 0 || off + 4 > WIN + (HFV_MUT_WINEDGE == 5 ? 2 : 0)) return g16(off) | g16(off + 2) << 16;
         const int a = off >> 2;   // row[a + 1] is at most the pad dword (zeroed), and then shifted out
         const uint64_t two = (uint64_t)row[a + 1] << 32 | row[a];
         return (uint32_t)(two >> (8 * (off & 3)));

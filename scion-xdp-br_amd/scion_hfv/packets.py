@@ -139,13 +139,32 @@ class Path:
 
 # ---- headers ---------------------------------------------------------------------------------
 
+def ref_host_addr_len(haddr: int) -> int:
+    """Bytes of host addresses the reference's parser skips after the two ISD-AS fields
+    (parser.h:133): 8 + 4*DL + 4*SL with SC_GET_DL = (haddr >> 2) & 0x2 and
+    SC_GET_SL = (haddr >> 6) & 0x2 (include/bpf/scion.h:50,52).  The 0x2 mask is a quirk of the
+    reference that every parser here keeps: it reads bit 3 of the DT/DL/ST/SL byte as the
+    destination length and bit 7 as the source length, each worth 8 more bytes, where the SCION
+    header has DL in bits 5-4 and SL in bits 1-0 ((len / 4) - 1).  So the reference parses 4- and
+    12-byte host addresses only, and only when those two bits say so."""
+    return 8 + 4 * ((haddr >> 2) & 0x2) + 4 * ((haddr >> 6) & 0x2)
+
+
+def host_addr_byte(dst_len: int, src_len: int) -> int:
+    """The DT/DL/ST/SL byte for host addresses of these lengths, type IP: the header's own
+    length fields, plus for a 12-byte address the bit the reference's parser reads instead
+    (ref_host_addr_len), so that it skips dst_len + src_len bytes for lengths of 4 and 12."""
+    haddr = ((dst_len // 4 - 1) << 4) | (src_len // 4 - 1)
+    return haddr | (0x08 if dst_len == 12 else 0) | (0x80 if src_len == 12 else 0)
+
+
 def scion_header(path_bytes, payload=PAYLOAD, dst_ia=(1, 0xFF0000000003), src_ia=(1, 0xFF0000000002),
                  dst_host=b"\x7f\x00\x00\x01", src_host=b"\x7f\x00\x00\x01", next_hdr=17, path_type=1,
                  version=0, haddr=None):
     """SCION common + address header + path + L4 payload.  haddr overrides the DT/DL/ST/SL byte
-    (default: derived from the host address lengths, type IP)."""
+    (default: host_addr_byte of the host address lengths)."""
     if haddr is None:
-        haddr = ((len(dst_host) // 4 - 1) << 4) | (len(src_host) // 4 - 1)
+        haddr = host_addr_byte(len(dst_host), len(src_host))
     hdr_len = 28 + len(dst_host) + len(src_host) + len(path_bytes)
     common = struct.pack(">BBHBBHBBH", (version << 4), 0, 0, next_hdr, hdr_len // 4, len(payload), path_type, haddr, 0)
     addr = struct.pack(">HHI", dst_ia[0], dst_ia[1] >> 32, dst_ia[1] & 0xFFFFFFFF)

@@ -48,8 +48,8 @@ def field_lines(frame, base):
     ip = 14
     v4 = frame[12:14] == b"\x08\x00"
     sc = ip + (4 * (frame[ip] & 0x0F) if v4 else 40) + 8
-    haddr = frame[sc + 9]
-    meta = sc + 28 + 8 + 4 * ((haddr >> 2) & 2) + 4 * ((haddr >> 6) & 2)
+    from scion_hfv import packets
+    meta = sc + 28 + packets.ref_host_addr_len(frame[sc + 9])
     spans = [(12, 2), (ip, 1), (ip + (9 if v4 else 6), 1), (sc, 1), (sc + 8, 2), (meta, 4), (inf, 8), (hf, 12)]
     lines = set()
     for off, size in spans:

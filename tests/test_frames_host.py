@@ -63,8 +63,7 @@ def ref_parse(f: bytes, end: int):
         return PARSE_ERROR, 0, 0, checked
     if struct.unpack_from(">I", f, sc)[0] >> 28 != 0:    # SC_GET_VER
         return NOT_IMPLEMENTED, 0, 0, checked
-    haddr = f[sc + 9]
-    data += 8 + 4 * ((haddr >> 2) & 0x2) + 4 * ((haddr >> 6) & 0x2)   # SC_GET_DL / SC_GET_SL (scion.h:50,52)
+    data += P.ref_host_addr_len(f[sc + 9])               # SC_GET_DL / SC_GET_SL (scion.h:50,52)
     if beyond(data):
         return PARSE_ERROR, 0, 0, checked
     if f[sc + 8] != 1:                                   # SC_PATH_TYPE_SCION

@@ -22,15 +22,17 @@ def _frame_mix(n, bad_every=0):
     return f
 
 
-def _oracle(frames, total, hf_check=True):
+def _oracle(frames, total, hf_check=True, lens=None, cfg=None, key=E.KEYS[1], rx_ifindex=E.RX_IFINDEX, slot=SLOT):
     """(rx, tx, tx_bytes, drop, digest, verdict counts) of the oracle router over the cyclic
-    sequence the producers push."""
+    sequence the producers push.  By default the evaluation setup's tables and ingress interface
+    and frames that fill their rows; `lens`, `cfg`, `key`, `rx_ifindex` and `slot` for another corpus."""
     n = frames.shape[0]
-    slots = np.zeros((n, SLOT), dtype=np.uint8)
+    slots = np.zeros((n, slot), dtype=np.uint8)
     slots[:, :frames.shape[1]] = frames
-    lens = np.full(n, frames.shape[1], dtype=np.uint16)
-    a, v, e, _ = orc.br_process(slots, lens, np.full(n, E.RX_IFINDEX, dtype=np.uint32), E.br_config()[0],
-                                orc.hop_key(E.KEYS[1]), hf_check=hf_check)
+    lens = np.full(n, frames.shape[1], dtype=np.uint16) if lens is None else np.asarray(lens, dtype=np.uint16)
+    a, v, e, _ = orc.br_process(slots, lens, np.full(n, rx_ifindex, dtype=np.uint32),
+                                E.br_config()[0] if cfg is None else cfg,
+                                orc.hop_key(key), hf_check=hf_check)
     reps = np.bincount(np.arange(total) % n, minlength=n).astype(np.uint64)
     tx = a == 4
     M = (1 << 64) - 1
