@@ -54,6 +54,22 @@ LaunchGeom br_geom(const hfv_ctx *ctx)
     g.br_split_cap = g_br_split;
     return g;
 }
+// hfv_debug_batch_grid: blocks per k_verify_batches launch (0 = one block per CU up to the tile
+// count), for every call that ends in launch_verify_batches.  With 1 to 3 blocks a list of a few
+// thousand tiles gives every wave a hundred tiles and more over many batches -- the dealing the real
+// grid reaches only at 2^24 records (tests/test_gpu_tile_deal.py).
+static unsigned g_batch_grid = 0;
+extern "C" int hfv_debug_batch_grid(unsigned blocks)
+{
+    g_batch_grid = blocks;
+    return 0;
+}
+LaunchGeom batch_geom(const hfv_ctx *ctx)
+{
+    LaunchGeom g = ctx->geom;
+    g.batch_grid_cap = g_batch_grid;
+    return g;
+}
 #endif
 
 int check_records(const hfv_ctx *ctx, const void *recs, size_t stride, const void *bits)
@@ -320,7 +336,7 @@ static int verify_records(hfv_ctx *ctx, const void *recs, size_t stride, size_t 
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
     return with_tables(ctx, (hipStream_t)stream, "verify_records launch", [&](DevState *ds) {
-        return launch_verify_records(ctx->geom, &ds->keys, &ctx->host_img->keys, ctx->keysel, (const uint8_t *)recs,
+        return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, (const uint8_t *)recs,
                                      stride, n, ctx->inf_off, ctx->hf_off, pass_bits, stream, ev0, ev1);
     });
 }
@@ -392,7 +408,7 @@ static int batches_launch(hfv_ctx *ctx, const struct hfv_batch *b, size_t count,
             a.cum[a.nb] = (uint32_t)tiles;
             a.total = (uint32_t)tiles;
             const bool fin = i >= last;
-            int e = launch_verify_batches(ctx->geom, ctx->keysel, a, st, ev0, fin ? ev1 : nullptr);
+            int e = launch_verify_batches(batch_geom(ctx), ctx->keysel, a, st, ev0, fin ? ev1 : nullptr);
             if (e != hipSuccess || fin) return e;   // with_tables notes the last launch
             note_reader(ctx, st);
             ev0 = nullptr;

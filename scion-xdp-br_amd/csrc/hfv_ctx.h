@@ -164,10 +164,14 @@ int after_launch(hfv_ctx *ctx, hipStream_t st, int err, const char *what);
 // records, stride and bitmap, the stride against the ctx's record layout (a call's own limits stay with it).
 int check_records(const hfv_ctx *ctx, const void *recs, size_t stride, const void *bits);
 // The router kernel's launch geometry: the ctx's, with the test build's hfv_debug_br_grid / br_split.
+// The batch-list launch's (launch_verify_batches, also behind launch_verify_records): the ctx's, with
+// the test build's hfv_debug_batch_grid.
 #ifdef HFV_TEST_HOOKS
 LaunchGeom br_geom(const hfv_ctx *ctx);
+LaunchGeom batch_geom(const hfv_ctx *ctx);
 #else
 #define br_geom(ctx) ((ctx)->geom)
+#define batch_geom(ctx) ((ctx)->geom)
 #endif
 
 #pragma GCC visibility pop

@@ -174,6 +174,8 @@ struct LaunchGeom {
     // always 0 in the product library): blocks per k_br_process launch, frames per split launch
     unsigned br_grid_cap = 0;
     uint64_t br_split_cap = 0;
+    // the same for the batch-list launch (hfv_debug_batch_grid): blocks per k_verify_batches launch
+    unsigned batch_grid_cap = 0;
 };
 
 // kernel launchers (hfv_kernels.hip); return hipError_t as int

@@ -296,6 +296,16 @@ __device__ __forceinline__ RecWords batch_load(const BatchTile &b, uint32_t g, u
 #ifndef HFV_BATCH_PIN
 #define HFV_BATCH_PIN 1
 #endif
+// HFV_MUT_TILEDEAL=N (make tiledeal; 0: the product): one deliberately wrong step in the tile dealing
+// of k_verify_batches, which tests/test_gpu_tile_deal.py must fail on.  Every mutant only masks
+// wrongly, or skips a store it owes to a bitmap: none moves a load or a store.
+//   1  the flush of 64 stashed verdict words leaves out lane 63's store
+//   2  the rec < n mask takes n from the newest mapped batch (the prefetched claim's), not the tile's own
+//   3  the fail-closed loop zeroes only each wave's first tile
+//   4  the LDS tile counter starts one too high: the block's 17th tile is never claimed
+#ifndef HFV_MUT_TILEDEAL
+#define HFV_MUT_TILEDEAL 0
+#endif
 template <int KEYSEL, int DEPTH>
 __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
 {
@@ -320,7 +330,11 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
             a->clk[1] = __builtin_amdgcn_s_memrealtime();
         }
     }
+#if HFV_MUT_TILEDEAL == 4
+    if (threadIdx.x == 0) s_next_tile = kWaves + 1;
+#else
     if (threadIdx.x == 0) s_next_tile = kWaves;
+#endif
     auto at = [&](uint32_t x) { return x < b1 ? x : last; };   // the tile a load reads for claim x
     auto claim = [&]() -> uint32_t {
         uint32_t c = 0;
@@ -372,12 +386,20 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
             batch_map(a, at(gg[in_slot]), bt[in_slot]);
             buf[in_slot] = batch_load(bt[in_slot], at(gg[in_slot]), lane, inf_off, hf_off);
             const uint64_t rec = (uint64_t)(gg[u] - bt[u].lo) * 64 + lane;
-            const uint64_t ballot = verify_tile<KEYSEL, HFV_BATCH_PIN != 0>(buf[u], rec < bt[u].n, l, &ukey);
+#if HFV_MUT_TILEDEAL == 2
+            const uint64_t n_own = bt[in_slot].n;
+#else
+            const uint64_t n_own = bt[u].n;
+#endif
+            const uint64_t ballot = verify_tile<KEYSEL, HFV_BATCH_PIN != 0>(buf[u], rec < n_own, l, &ukey);
             if (lane == stashed) {
                 st_word = ballot;
                 st_addr = bt[u].bits + (uint64_t)(gg[u] - bt[u].lo) * 8;
             }
             if (++stashed == 64) {
+#if HFV_MUT_TILEDEAL == 1
+                if (lane != 63)
+#endif
                 *(GlobalU64 *)st_addr = st_word;
                 stashed = 0;
             }
@@ -390,6 +412,9 @@ done:
         for (uint32_t g = b0 + wv; g < b1; g += kWaves) {
             batch_map(a, g, bt[0]);
             if (lane == 0) *(GlobalU64 *)(bt[0].bits + (uint64_t)(g - bt[0].lo) * 8) = 0;
+#if HFV_MUT_TILEDEAL == 3
+            break;
+#endif
         }
     }
     if (lane == 0 && a->clk)   // the block's last wave to leave sets its finish stamp
@@ -409,6 +434,7 @@ int launch_verify_batches(const LaunchGeom &g, int keysel, const BatchArgs &args
     // one block per CU, but no more blocks than tiles: every block owns at least one tile
     uint64_t blocks = args.total;
     if (blocks > (uint64_t)g.num_cus) blocks = (uint64_t)g.num_cus;
+    if (g.batch_grid_cap && g.batch_grid_cap < blocks) blocks = g.batch_grid_cap;   // test build only
     hipExtLaunchKernelGGL(k, dim3((unsigned)(blocks ? blocks : 1)), dim3(kBlock), 0, (hipStream_t)stream,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0u, args);
     return (int)hipGetLastError();
