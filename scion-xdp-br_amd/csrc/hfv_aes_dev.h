@@ -1,5 +1,6 @@
 // hfv_aes_dev.h -- device-side AES-128 / CMAC building blocks shared by the gfx950 kernels
-// (record verify in hfv_kernels.hip, full border-router path in hfv_br_kernel.hip).
+// (record verify in hfv_verify_kernels.hip, hfv_service_kernel.hip and hfv_aux_kernels.hip, full
+// border-router path in hfv_br_kernel.hip).
 // Each translation unit gets its own copy of the LDS arrays and the constant T0 table
 // (internal linkage); a kernel's LDS allocation counts only the arrays it touches.
 #pragma once

@@ -1,5 +1,5 @@
 // hfv_internal.h -- shared between the host code (the units around hfv_ctx.h, hfv_aes_host.cpp)
-// and the kernel launchers (hfv_kernels.hip).  Not installed.
+// and the kernel launchers (the .hip units).  Not installed.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -109,7 +109,7 @@ enum KernelMode { kModeRecords = 0, kModeMacinputs = 1, kModeTags = 2 };
 // batch on a box whose host round trips were slow).  Batch b (0-based, ticket
 // b+1) uses ring slot b % kSvcRing; the host posts ticket t only once ticket t - kSvcRing is
 // complete, which is what lets each block cache kSvcRing descriptors in LDS without any reuse
-// check (hfv_kernels.hip, k_verify_service).  A grid that exits on its stop descriptor has
+// check (hfv_service_kernel.hip, k_verify_service).  A grid that exits on its stop descriptor has
 // verified every batch before it, so the host needs no forwarded completion for those.
 constexpr uint32_t kSvcRing = 128;   // batches in flight (a host hiccup of ~1.5 ms at 2^20 records does not starve the grid;
                                      // 128 x 64 B of descriptor cache per block leaves LDS room for config 3's key rows)
@@ -178,7 +178,9 @@ struct LaunchGeom {
     unsigned batch_grid_cap = 0;
 };
 
-// kernel launchers (hfv_kernels.hip); return hipError_t as int
+// kernel launchers; return hipError_t as int.  Record and batch-list verify, key_prologue:
+// hfv_verify_kernels.hip; the service and query_geometry: hfv_service_kernel.hip; macinputs, tags,
+// key expansion, verdict counts, record generator, stream read: hfv_aux_kernels.hip.
 // interleaved: grid-stride tile order (wave w takes tiles w, w + W, ...) instead of one
 // contiguous tile range per block -- for records in host memory, where the 256 ranges far
 // apart thrash the GPU's translation of 4 KiB host pages (zero-copy 2^20: 1.60 -> 1.27 ms)

@@ -1,5 +1,5 @@
 // hfv_service.cpp -- the resident verify service (hfv_service_*).
-// The host side of k_verify_service (hfv_kernels.hip): tickets 1, 2, ... go to ring slot
+// The host side of k_verify_service (hfv_service_kernel.hip): tickets 1, 2, ... go to ring slot
 // (t - 1) % kSvcRing; ticket t is posted only once ticket t - kSvcRing is done.  Ring and
 // completion words hold svc_tag | t, the tag changing with every grid, so nothing is cleared
 // between grids.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """ISA census of a kernel's hot loop (gfx950 .s from `make asm`).
 
-    python scripts/isa_loop.py build/hfv_kernels-hip-amdgcn-amd-amdhsa-gfx950.s SYMBOL_SUBSTRING
+    python scripts/isa_loop.py build/hfv_verify_kernels-hip-amdgcn-amd-amdhsa-gfx950.s SYMBOL_SUBSTRING
 
 Finds the function, then the loop (header .. back-edge) holding the most ds_read instructions,
 walks it in program order and reports: instruction counts by class (LDS reads, other LDS ops,
