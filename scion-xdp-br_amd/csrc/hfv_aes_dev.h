@@ -27,19 +27,16 @@ static __constant__ uint32_t c_t0[256] = {T0V64(0), T0V64(64), T0V64(128), T0V64
 // four (128 KiB) and needs no rotation.
 static __shared__ uint32_t s_tab64[16384];
 static __shared__ uint32_t s_tab128[32768];
-// TAB = 3: T0/T1 with kTab3Copies lane copies (4: 8 KiB) for kernels where AES is a small
-// part of the work and LDS is needed for other things (the router kernel): byte address
+// TAB = 3: T0/T1 with kTab3Copies lane copies (8: 16 KiB) for the router kernel, where AES is a
+// small part of the work and LDS is needed for other things: byte address
 //   (t << (10 + log2 copies)) | (x << (2 + log2 copies)) | ((L % copies) << 2)
 // formed with a shift instead of v_perm.  The table bit sits above the bank bits, so the
-// lanes that share a copy spread over 32 / copies banks by x (at 4 copies: 8 lanes of a
-// 32-lane half over 8 banks); lanes of one copy still conflict when their x differ in the
-// bank bits' range.  A translation unit may define HFV_TAB3_COPIES before including this header.
-#ifndef HFV_TAB3_COPIES
-#define HFV_TAB3_COPIES 16
-#endif
-constexpr uint32_t kTab3Copies = HFV_TAB3_COPIES;
+// lanes that share a copy spread over 32 / copies banks by x (at 8 copies: 4 lanes of a
+// 32-lane half over 4 banks); lanes of one copy still conflict when their x differ in the
+// bank bits' range.  (4 and 16 copies were measured with other LDS budgets: DESIGN 4.1.)
+constexpr uint32_t kTab3Copies = 8;
 constexpr uint32_t kTab3Log = kTab3Copies == 32 ? 5 : kTab3Copies == 16 ? 4 : kTab3Copies == 8 ? 3 : kTab3Copies == 4 ? 2 : 99;
-static_assert(kTab3Log < 8, "HFV_TAB3_COPIES must be 4, 8, 16 or 32");
+static_assert(kTab3Log < 8, "kTab3Copies must be 4, 8, 16 or 32");
 static __shared__ uint32_t s_tab32[256 * 2 * kTab3Copies];
 static __shared__ uint4 s_keys[kDevKeyRows * HFV_MAX_KEYS];   // 48 KiB, round-major
 static __shared__ uint32_t s_valid[8];

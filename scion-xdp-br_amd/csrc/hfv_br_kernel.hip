@@ -17,7 +17,7 @@
 // part of the router's work, so LDS goes to header rows),
 // and stages the router tables (~6.5 KiB), its verdict counters (5.5 KiB of 32-bit words) and, in
 // the staged variant, the first 128 bytes of each frame of its waves' tiles (a frame whose header
-// runs past them also gets bytes 128-135 in registers, HFV_BR_EXT).  The rewrite patches the
+// runs past them also gets bytes 128-135 in registers, BrFrame::ext).  The rewrite patches the
 // staged rows, and only the 16-byte chunks it touched go back to HBM; payload bytes are never
 // read.  At most one hop field is checked per frame (ingress from a neighbour AS or
 // egress of a packet from the own AS), with the record-verify kernel's AES code (slot-0 key
@@ -26,30 +26,9 @@
 #include <hip/hip_ext.h>
 #include <stdlib.h>
 
-// Staging waves per CU: 16 (AES tables with 4 lane copies, to fit the 16 header-row buffers in
-// LDS; VGPRs capped at 128, which the frame state fits since the rewrite reads its inputs from
-// the staged row and the tables: 124, no scratch) or 12 (16 copies; 14 % slower).
-#ifndef HFV_BR_WAVES
-#define HFV_BR_WAVES 16
-#endif
-// HFV_BR_STATS32 = 1: the block's verdict counters in 32-bit LDS words (5.5 KiB instead of 11),
-// added into the caller's 64-bit counters at the end of the launch; launch_br_process splits a
-// launch so that no block can count 2^32 bytes.  The LDS this frees holds 8 lane copies of the
-// AES tables instead of 4.
-#ifndef HFV_BR_STATS32
-#define HFV_BR_STATS32 1
-#endif
-#ifndef HFV_TAB3_COPIES
-#if HFV_BR_WAVES == 16 && HFV_BR_STATS32
-#define HFV_TAB3_COPIES 8
-#elif HFV_BR_WAVES == 16
-#define HFV_TAB3_COPIES 4
-#else
-#define HFV_TAB3_COPIES 16
-#endif
-#endif
 #include "hfv_aes_dev.h"
 #include "hfv_internal.h"
+#include "hfv_wave_sync.h"
 
 // HFV_MUT_WINEDGE = 1..7 (`make winedge`): deliberately wrong window-edge cases in the access
 // helpers below (1 rd32, 2 and 7 wr32's HBM and LDS half, 3 in_ext, 4 beyond, 6 rd16; 5 is
@@ -65,64 +44,26 @@
 namespace hfv {
 
 static __shared__ DevBrConfig s_br;
-#if HFV_BR_STATS32
+// The block's verdict counters in 32-bit LDS words (5.5 KiB instead of 11; the LDS this frees
+// holds 8 lane copies of the AES tables instead of 4), added into the caller's 64-bit counters at
+// the end of the launch; launch_br_process splits a launch so that no block can count 2^32 bytes
+// ("32-bit block counters").
 typedef uint32_t BrCount;
-#else
-typedef unsigned long long BrCount;
-#endif
 static __shared__ BrCount s_stats[HFV_BR_STATS_IFINDEX * 2 * HFV_BR_COUNTERS];
 
 // Header staging (WIN > 0 kernels): the first kBrWin bytes of each frame of a wave's 64-frame
 // tile, one row of kBrWin / 4 + 1 dwords per frame (the odd row pitch keeps both the staging
-// writes and the per-lane reads bank-conflict free), for up to kBrStageWaves waves per block.
+// writes and the per-lane reads bank-conflict free), for the kBrStageWaves waves of a block: 16,
+// with VGPRs capped at 128, which the frame state fits since the rewrite reads its inputs from
+// the staged row and the tables (124, no scratch; 12 waves with 16 table copies: DESIGN 4.1).
 constexpr int kBrWin = 128;
 constexpr int kBrRow = kBrWin / 4 + 1;
-constexpr int kBrStageWaves = HFV_BR_WAVES;
+constexpr int kBrStageWaves = 16;
 static __shared__ uint32_t s_hdr[kBrStageWaves * 64 * kBrRow];
-
-// HFV_BR_PROF = 1: diagnostic build.  Each wave adds the shader cycles (s_memtime) it spends in
-// the phases of a tile into g_br_prof (read by hfv_debug_br_prof): [0] header loads issued ->
-// staged, [1] parse/process_packet, [2] MAC check + outputs, [3] write-back, [4] tiles.
-#ifndef HFV_BR_PROF
-#define HFV_BR_PROF 0
-#endif
-// HFV_BR_WB: order of a tile's write-back against the next tile's header loads.
-//   0: stores, then the next tile's loads at the top of the loop (vmcnt retires in order, so
-//      the wait for the loads also waits for the stores' acknowledgement);
-//   1: the changed chunks are read from LDS into registers, the next tile's loads are issued,
-//      then the chunks go out as buffer stores whose lanes without a change address past the
-//      tile's buffer range (dropped by the bounds check: no branch, a fixed count of stores), and
-//      the loop waits for the loads only (vmcnt = that count);
-//   9: diagnostic, no write-back at all (wrong output: measures what the stores cost).
-#ifndef HFV_BR_WB
-#define HFV_BR_WB 1
-#endif
-// HFV_BR_DYN (with HFV_BR_WB == 1): 1 = each block owns a contiguous tile range and its waves
-// claim the next tile from a block-local LDS counter at the end of the current one, so a wave
-// that ran fast takes more; 0 = tile t goes to wave (t mod waves) statically.
-#ifndef HFV_BR_DYN
-#define HFV_BR_DYN 1
-#endif
+// Staged kernels: each block owns a contiguous tile range and its waves claim the next tile from
+// this counter at the end of the current one, so a wave that ran fast takes more (DESIGN 4.1,
+// "Tiles per block, claimed").
 static __shared__ uint32_t s_br_next;
-#if HFV_BR_PROF
-__device__ unsigned long long g_br_prof[8];
-#endif
-struct BrProf {
-    uint64_t c[5] = {0, 0, 0, 0, 0};
-    uint64_t t = 0;
-    __device__ __forceinline__ void start()
-    {
-        if constexpr (HFV_BR_PROF) t = __builtin_amdgcn_s_memtime();
-    }
-    __device__ __forceinline__ void mark(int i)
-    {
-        if constexpr (HFV_BR_PROF) {
-            const uint64_t x = __builtin_amdgcn_s_memtime();
-            c[i] += x - t;
-            t = x;
-        }
-    }
-};
 
 // enum xdp_action and enum verdict (br/src/bpf/common.h:38-70)
 enum : uint32_t { A_ABORTED = 0, A_DROP = 1, A_PASS = 2, A_TX = 3, A_REDIRECT = 4 };
@@ -135,11 +76,13 @@ enum : uint32_t {
 };
 
 // The BPF code reads and writes network-order fields through little-endian u16/u32 views.
-__device__ __forceinline__ uint32_t g8(const uint8_t *q) { return q[0]; }
-__device__ __forceinline__ uint32_t g16(const uint8_t *q) { return (uint32_t)q[0] | ((uint32_t)q[1] << 8); }
-__device__ __forceinline__ uint32_t g32(const uint8_t *q)
+template <int N>
+__device__ __forceinline__ uint32_t gle(const uint8_t *q)   // N bytes from HBM, unaligned
 {
-    return (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+    uint32_t v = q[0];
+#pragma unroll
+    for (int b = 1; b < N; ++b) v |= (uint32_t)q[b] << (8 * b);
+    return v;
 }
 __device__ __forceinline__ uint32_t sw16(uint32_t v) { return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu); }
 __device__ __forceinline__ uint32_t sw32(uint32_t v) { return __builtin_bswap32(v); }
@@ -151,7 +94,7 @@ struct BrFrame {
     uint32_t row;      // dword index of this frame's staged header row in s_hdr
     int win;           // staged bytes (0: read and write everything in HBM)
     // bytes win..win+7, loaded into registers at the start of the frame when its SCION header
-    // (HdrLen) runs past the window (HFV_BR_EXT): one early load instead of a round trip per field
+    // (HdrLen) runs past the window (load_ext): one early load instead of a round trip per field
     uint32_t ext[2];
     bool has_ext;
     uint32_t dirty;    // 16-byte chunks of the staged row written (only those go back to HBM)
@@ -194,42 +137,6 @@ __device__ __forceinline__ uint32_t lds_u32_at(const BrFrame &k, int off)
     int a = off >> 2;
     return __builtin_amdgcn_alignbyte(row[a + 1], row[a], (uint32_t)(off & 3));
 }
-// The wait for a read past the window sits inside its branch: placed after the merge by the
-// waitcnt pass, a vmcnt(0) would run on every path and wait for the previous tile's write-back
-// stores, which vmcnt retires in order before this read (HFV_BR_WB == 1 leaves them in flight).
-__device__ __forceinline__ void wait_past_window() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // vmcnt(0)
-// HFV_BR_EXT = 1: frames whose SCION header (by its HdrLen) ends past the window get the next 8
-// bytes (the bench mix's longest headers end at 136) with one load issued before the parse; their
-// reads of those bytes come from registers.
-#ifndef HFV_BR_EXT
-#define HFV_BR_EXT 1
-#endif
-constexpr int kBrExt = 8;
-// the 32 bits starting at byte b (0 <= b <= 4, or b <= 6 for the low 16) of the frame's ext bytes
-__device__ __forceinline__ uint32_t ext_u32(const BrFrame &k, int b)
-{
-    if (HFV_MUT_WINEDGE == 3 && b > 6) b = 6;   // the mutant's two extra bytes: clamped into the registers
-    return __builtin_amdgcn_alignbyte(k.ext[1], b < 4 ? k.ext[0] : k.ext[1], (uint32_t)b & 3u);
-}
-__device__ __forceinline__ bool in_ext(const BrFrame &k, int off, int size)
-{
-    return HFV_BR_EXT && k.has_ext && off >= k.win && off + size <= k.win + kBrExt + (HFV_MUT_WINEDGE == 3 ? 2 : 0);
-}
-__device__ __forceinline__ uint32_t rd8(const BrFrame &k, int off)
-{
-    if (k.win == 0) return g8(k.p + off);
-    const bool in = (uint32_t)off < (uint32_t)k.win;
-    uint32_t v = reinterpret_cast<const uint8_t *>(s_hdr + k.row)[in ? off : 0];
-    if (!in) {
-        if (in_ext(k, off, 1)) {
-            v = ext_u32(k, off - k.win) & 0xffu;
-        } else {
-            v = g8(k.p + off);
-            wait_past_window();
-        }
-    }
-    return v;
-}
 // Every 16- and 32-bit header field sits at an even offset (Ethernet 14 B, IP header lengths in
 // 4-byte units, UDP 8, SCION common header 12, host addresses in 4-byte units, info fields 8 and
 // hop fields 12 B), so a 16-bit field is one ds_read_u16 / ds_write_b16 of the staged row
@@ -239,91 +146,95 @@ __device__ __forceinline__ uint32_t lds_u16_at(const BrFrame &k, int off)
 {
     return *reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(s_hdr + k.row) + off);
 }
-__device__ __forceinline__ uint32_t rd16(const BrFrame &k, int off)
+// The wait for a read past the window sits inside its branch: placed after the merge by the
+// waitcnt pass, a vmcnt(0) would run on every path and wait for the previous tile's write-back
+// stores, which vmcnt retires in order before this read (the tile loop leaves them in flight).
+__device__ __forceinline__ void wait_past_window() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // vmcnt(0)
+// Frames whose SCION header (by its HdrLen) ends past the window get the next 8 bytes (the bench
+// mix's longest headers end at 136) with one load issued before the parse (load_ext); their reads
+// of those bytes come from registers ("Only the frames that need it").
+constexpr int kBrExt = 8;
+// the 32 bits starting at byte b (0 <= b <= 4, or b <= 6 for the low 16) of the frame's ext bytes
+__device__ __forceinline__ uint32_t ext_u32(const BrFrame &k, int b)
 {
-    if (k.win == 0) return g16(k.p + off);
-    const bool in = (uint32_t)off + 2 <= (uint32_t)k.win + (HFV_MUT_WINEDGE == 6 ? 2u : 0u);   // mutant: the pad dword
-    uint32_t v = lds_u16_at(k, in ? off : 0);
+    if (HFV_MUT_WINEDGE == 3 && b > 6) b = 6;   // the mutant's two extra bytes: clamped into the registers
+    return __builtin_amdgcn_alignbyte(k.ext[1], b < 4 ? k.ext[0] : k.ext[1], (uint32_t)b & 3u);
+}
+__device__ __forceinline__ bool in_ext(const BrFrame &k, int off, int size)
+{
+    return k.has_ext && off >= k.win && off + size <= k.win + kBrExt + (HFV_MUT_WINEDGE == 3 ? 2 : 0);
+}
+// The one read rule, for a field of N = 1, 2 or 4 bytes.
+template <int N>
+__device__ __forceinline__ uint32_t rd(const BrFrame &k, int off)
+{
+    static_assert(N == 1 || N == 2 || N == 4, "field size");
+    if (k.win == 0) return gle<N>(k.p + off);
+    // The whole field inside the window?  Spelled out here and in wr: through a shared helper
+    // function the compiler generated other code.  (Mutant 1: a 32-bit field across the window end
+    // is read from the row and its pad dword; mutant 6: a 16-bit field is read from the pad dword.)
+    const bool in = N == 1   ? (uint32_t)off < (uint32_t)k.win
+                    : N == 2 ? (uint32_t)off + 2 <= (uint32_t)k.win + (HFV_MUT_WINEDGE == 6 ? 2u : 0u)
+                             : (uint32_t)off + 4 <= (uint32_t)k.win || (HFV_MUT_WINEDGE == 1 && (uint32_t)off < (uint32_t)k.win);
+    uint32_t v = N == 1   ? reinterpret_cast<const uint8_t *>(s_hdr + k.row)[in ? off : 0]
+                 : N == 2 ? lds_u16_at(k, in ? off : 0)
+                          : lds_u32_at(k, in ? off : 0);
     if (!in) {
-        if (in_ext(k, off, 2)) {
-            v = ext_u32(k, off - k.win) & 0xffffu;
+        if (in_ext(k, off, N)) {
+            v = ext_u32(k, off - k.win) & (uint32_t)((1ull << 8 * N) - 1);
         } else {
-            v = g16(k.p + off);
+            v = gle<N>(k.p + off);
             wait_past_window();
         }
     }
     return v;
 }
-__device__ __forceinline__ uint32_t rd32(const BrFrame &k, int off)
-{
-    if (k.win == 0) return g32(k.p + off);
-    // (mutant 1: a field across the window end is read from the row and its pad dword)
-    const bool in = (uint32_t)off + 4 <= (uint32_t)k.win || (HFV_MUT_WINEDGE == 1 && (uint32_t)off < (uint32_t)k.win);
-    uint32_t v = lds_u32_at(k, in ? off : 0);
-    if (!in) {
-        if (in_ext(k, off, 4)) {
-            v = ext_u32(k, off - k.win);
-        } else {
-            v = g32(k.p + off);
-            wait_past_window();
-        }
-    }
-    return v;
-}
+__device__ __forceinline__ uint32_t rd8(const BrFrame &k, int off) { return rd<1>(k, off); }
+__device__ __forceinline__ uint32_t rd16(const BrFrame &k, int off) { return rd<2>(k, off); }
+__device__ __forceinline__ uint32_t rd32(const BrFrame &k, int off) { return rd<4>(k, off); }
 
 // Header writes: bytes inside the staged window go to the LDS row (written back to HBM with
 // coalesced 16-byte stores at the end of the tile), bytes past it straight to HBM.  As with the
 // reads, the LDS store is unconditional: a field not wholly inside the window is stored into
 // the row's pad dword (bytes kBrWin..kBrWin+3, never read for a result nor written back) and
-// then handled on the rare branch.
+// then handled on the rare branch: whole to HBM if it starts past the window, in two halves by
+// this same rule if it lies across the window's end.
 constexpr int kBrPad = kBrWin;
 __device__ __forceinline__ uint32_t chunk_bit(int off) { return 1u << ((uint32_t)off >> 4 & 31u); }
-__device__ __forceinline__ void wr8(BrFrame &k, int off, uint32_t v)
+__device__ __forceinline__ void put_le(uint8_t *q, int n, uint32_t v)   // n bytes to HBM, unaligned
 {
-    if (k.win == 0) { k.po[off] = (uint8_t)v; return; }
-    const bool in = (uint32_t)off < (uint32_t)k.win;
-    reinterpret_cast<uint8_t *>(s_hdr + k.row)[in ? off : kBrPad] = (uint8_t)v;
-    k.dirty |= in ? chunk_bit(off) : 0u;
-    if (!in) k.po[off] = (uint8_t)v;
+#pragma unroll
+    for (int b = 0; b < n; ++b) q[b] = (uint8_t)(v >> (8 * b));
 }
-__device__ __forceinline__ void wr16(BrFrame &k, int off, uint32_t v)
+template <int N>
+__device__ __forceinline__ void wr(BrFrame &k, int off, uint32_t v)
 {
-    if (k.win == 0) { k.po[off] = (uint8_t)v; k.po[off + 1] = (uint8_t)(v >> 8); return; }
-    const bool in = (uint32_t)off + 2 <= (uint32_t)k.win;   // whole field in the window (the common case)
+    static_assert(N == 1 || N == 2 || N == 4, "field size");
+    if (k.win == 0) { put_le(k.po + off, N, v); return; }
+    const bool in = N == 1 ? (uint32_t)off < (uint32_t)k.win : (uint32_t)off + N <= (uint32_t)k.win;   // whole field in the window
     uint8_t *q = reinterpret_cast<uint8_t *>(s_hdr + k.row) + (in ? off : kBrPad);
-    *reinterpret_cast<uint16_t *>(q) = (uint16_t)v;
-    k.dirty |= in ? chunk_bit(off) | chunk_bit(off + 1) : 0u;
+    if constexpr (N == 1) {
+        *q = (uint8_t)v;
+    } else {   // ds_write_b16: fields are 2-byte aligned (above)
+        reinterpret_cast<uint16_t *>(q)[0] = (uint16_t)v;
+        if constexpr (N == 4) reinterpret_cast<uint16_t *>(q)[1] = (uint16_t)(v >> 16);
+    }
+    k.dirty |= in ? chunk_bit(off) | chunk_bit(off + N - 1) : 0u;
     if (!in) {
-        if (off >= k.win) {
-            k.po[off] = (uint8_t)v; k.po[off + 1] = (uint8_t)(v >> 8);
+        if constexpr (N == 1) {
+            k.po[off] = (uint8_t)v;
+        } else if (off >= k.win) {
+            put_le(k.po + off, N, v);
         } else {
-            wr8(k, off, v);
-            wr8(k, off + 1, v >> 8);
+            // mutants 7 and 2: a 32-bit field across the window end loses its LDS or its HBM half
+            if (!(N == 4 && HFV_MUT_WINEDGE == 7)) wr<N / 2>(k, off, v);
+            if (!(N == 4 && HFV_MUT_WINEDGE == 2 && off + 2 >= k.win)) wr<N / 2>(k, off + N / 2, v >> (4 * N));
         }
     }
 }
-__device__ __forceinline__ void wr32(BrFrame &k, int off, uint32_t v)
-{
-    if (k.win == 0) {
-        uint8_t *q = k.po + off;
-        q[0] = (uint8_t)v; q[1] = (uint8_t)(v >> 8); q[2] = (uint8_t)(v >> 16); q[3] = (uint8_t)(v >> 24);
-        return;
-    }
-    const bool in = (uint32_t)off + 4 <= (uint32_t)k.win;
-    uint8_t *q = reinterpret_cast<uint8_t *>(s_hdr + k.row) + (in ? off : kBrPad);
-    reinterpret_cast<uint16_t *>(q)[0] = (uint16_t)v;
-    reinterpret_cast<uint16_t *>(q)[1] = (uint16_t)(v >> 16);
-    k.dirty |= in ? chunk_bit(off) | chunk_bit(off + 3) : 0u;
-    if (!in) {
-        if (off >= k.win) {
-            uint8_t *h = k.po + off;
-            h[0] = (uint8_t)v; h[1] = (uint8_t)(v >> 8); h[2] = (uint8_t)(v >> 16); h[3] = (uint8_t)(v >> 24);
-        } else {
-            if (HFV_MUT_WINEDGE != 7) wr16(k, off, v);
-            if (!(HFV_MUT_WINEDGE == 2 && off + 2 >= k.win)) wr16(k, off + 2, v >> 16);
-        }
-    }
-}
+__device__ __forceinline__ void wr8(BrFrame &k, int off, uint32_t v) { wr<1>(k, off, v); }
+__device__ __forceinline__ void wr16(BrFrame &k, int off, uint32_t v) { wr<2>(k, off, v); }
+__device__ __forceinline__ void wr32(BrFrame &k, int off, uint32_t v) { wr<4>(k, off, v); }
 
 // Bounds check of the BPF code ("data + n > data_end").  With a header window smaller than the
 // frame, running past the window marks the frame `cut` (the host path re-runs it whole).
@@ -783,14 +694,13 @@ __device__ __forceinline__ bool tx_port(int ifindex)
     return (s_br.tx_bits[ifindex >> 5] >> (ifindex & 31)) & 1u;
 }
 
-// ---- kernel ------------------------------------------------------------------------------------
+// ---- xdp.c: border_router, one frame -------------------------------------------------------
 template <bool STATS>
 __device__ __forceinline__ void br_frame(BrFrame &k, uint64_t i, const DevKeyTable *keys,
                                          uint8_t *__restrict__ action, uint8_t *__restrict__ verdict,
-                                         int32_t *__restrict__ egress, BrProf &prof)
+                                         int32_t *__restrict__ egress)
 {
     int a = process_packet<STATS>(k);
-    prof.mark(1);
     if (k.cut) {   // headers reach past the window: untouched, uncounted, caller re-runs it whole
         action[i] = HFV_BR_ACTION_RETRY;
         verdict[i] = 0;
@@ -833,10 +743,82 @@ __device__ __forceinline__ void br_frame(BrFrame &k, uint64_t i, const DevKeyTab
     egress[i] = k.egress_ifindex;
 }
 
-// One wave = one tile of 64 consecutive frames (lane = frame).  WIN > 0: the tile's first WIN
-// header bytes per frame are fetched with coalesced 16-byte loads (WIN / 16 frames' chunks per
-// wave instruction... 64 / (WIN / 16) frames per instruction), staged in LDS and parsed from
-// there, and the next tile's bytes are already in flight while this one is parsed.
+// ---- the tile loop's steps ------------------------------------------------------------------
+// One wave = one tile of 64 consecutive frames (lane = frame).  Staged kernels fetch the tile's
+// first kBrWin header bytes per frame with coalesced 16-byte loads (kBrChunks lanes per frame,
+// kBrRound frames per wave instruction), stage them in LDS and parse them from there, and the
+// next tile's bytes are already in flight while this one is written back.
+constexpr int kBrChunks = kBrWin / 16;      // 16-byte chunks of a staged row
+constexpr int kBrRound = 64 / kBrChunks;    // frames one wave load or store instruction covers
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+
+struct BrTile {   // what is loaded ahead for a tile
+    uint4 hdr[kBrChunks];   // the staging lane's chunk of kBrChunks frames
+    uint32_t len, ifx;      // the lane's own frame
+};
+
+// nf frames from frame 64 * t of `base` as a buffer: a load past them returns zeros and a store
+// past them is dropped, neither touching memory (kPastBuffer: an offset no tile reaches, since a
+// tile of 64 slots is addressed through 32-bit offsets below 2^31, launch_br_process).
+constexpr uint32_t kPastBuffer = 0x80000000u;
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const uint8_t *base, uint64_t t, uint32_t nf, uint64_t slot)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(base) + t * 64 * slot, 0, (int)(nf * (uint32_t)slot),
+                                             0x00020000);
+}
+__device__ __forceinline__ uint4 load_chunk(__amdgpu_buffer_rsrc_t rs, uint32_t off)
+{
+    // the whole offset in the VGPR: the bounds check does not cover soffset
+    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)off, 0, 0);
+    return make_uint4(v.x, v.y, v.z, v.w);
+}
+
+// Chunk ch of frame fr in a wave's staged rows, and its dwords in and out of LDS.
+__device__ __forceinline__ uint32_t *row_chunk(uint32_t *rows, uint32_t fr, uint32_t ch) { return rows + fr * kBrRow + 4 * ch; }
+__device__ __forceinline__ void put_chunk(uint32_t *d, const uint4 &v) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }
+__device__ __forceinline__ v4u get_chunk(const uint32_t *q) { return v4u{q[0], q[1], q[2], q[3]}; }
+
+// The lane's own length and ingress ifindex (unconditional: lanes past the batch are masked at use).
+__device__ __forceinline__ void fetch_lane(const uint16_t *lens, const uint32_t *ifidx, uint64_t n, uint32_t lane,
+                                           uint64_t t, BrTile &x)
+{
+    uint64_t fi = t * 64 + lane;
+    if (fi >= n) fi = n - 1;
+    x.len = lens[fi];
+    x.ifx = ifidx[fi];
+}
+
+// Bytes kBrWin..kBrWin+7 of a frame whose SCION header ends past the window, by its HdrLen (sc + 5;
+// sc after Ethernet, IPv4 with its IHL or IPv6, and UDP): a hint only, every read still checks
+// its own bounds.  Every other lane's load addresses past the buffer (no memory access).
+__device__ __forceinline__ void load_ext(const uint8_t *pkts, uint64_t slot, uint64_t n, uint32_t lane, uint64_t t,
+                                         BrFrame &k)
+{
+    const uint32_t proto = lds_u16_at(k, 12);
+    const int udp = proto == 0x0008u ? 14 + 4 * (int)(lds_u16_at(k, 14) & 0x0fu) : 54;
+    const int sc = udp + 8;
+    const int end = sc + 4 * (int)(reinterpret_cast<const uint8_t *>(s_hdr + k.row)[sc + 5 < kBrWin ? sc + 5 : 0]);
+    k.has_ext = k.lim > kBrWin && sc + 5 < kBrWin && end > kBrWin && (proto == 0x0008u || proto == 0xdd86u);
+    const uint64_t left = n - t * 64;
+    const uint32_t nf = left < 64 ? (uint32_t)left : 64u;
+    const __amdgpu_buffer_rsrc_t rx = tile_rsrc(pkts, t, nf, slot);
+    const v2u e = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)(k.has_ext ? lane * (uint32_t)slot + kBrWin : kPastBuffer), 0, 0);
+    k.ext[0] = e.x; k.ext[1] = e.y;
+}
+
+// The next of the block's tiles [tb0, tb1), handed out by s_br_next (ntiles: nothing left).
+__device__ __forceinline__ uint64_t claim_tile(uint32_t lane, uint64_t tb0, uint64_t tb1, uint64_t ntiles)
+{
+    uint32_t g = 0;
+    if (lane == 0) g = __hip_atomic_fetch_add(&s_br_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    const uint64_t t = tb0 + __builtin_amdgcn_readfirstlane(g);
+    return t < tb1 ? t : ntiles;
+}
+
+// ---- k_br_process ---------------------------------------------------------------------------
+// WIN = kBrWin: the staged kernel.  WIN = 0: the direct kernel, every header byte read from and
+// written to HBM, tiles dealt statically.
 template <int BLOCK, bool STATS, int WIN>
 __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict__ st, const uint8_t *pkts,
                                                       uint8_t *out,
@@ -848,8 +830,8 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
                                                       unsigned long long *__restrict__ stats)
 {
     static_assert(WIN == 0 || (WIN == kBrWin && BLOCK / 64 <= kBrStageWaves), "staging geometry");
-    constexpr int C = WIN > 0 ? WIN / 16 : 1;   // 16-byte chunks per frame
-    fill_ttab<3>();   // 32 KiB (AES is a small part of the router's work; LDS goes to header rows)
+    constexpr bool kStaged = WIN > 0;
+    fill_ttab<3>();   // 16 KiB (AES is a small part of the router's work; LDS goes to header rows)
     {
         const uint4 *src = reinterpret_cast<const uint4 *>(&st->br);
         uint4 *dst = reinterpret_cast<uint4 *>(&s_br);
@@ -862,8 +844,8 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
 
     const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
     const uint64_t ntiles = (n + 63) / 64, nwaves = (uint64_t)gridDim.x * (BLOCK / 64);
-    // Tiles go round the blocks first (wave w of block b starts at tile w * grid + b), so a
-    // launch of fewer tiles than waves (the config-5 loop's 64 Ki-frame chunks: 1024 tiles)
+    // Static deal (the direct kernel, and the detached loop): tiles go round the blocks first
+    // (wave w of block b starts at tile w * grid + b), so a launch of fewer tiles than waves
     // still spreads over every CU instead of filling a quarter of them with 16 waves each.
     // (wave-uniform as far as the compiler knows: the buffer resources built from it stay in SGPRs)
     uint64_t t = (uint64_t)__builtin_amdgcn_readfirstlane(wib) * gridDim.x + blockIdx.x;
@@ -878,92 +860,52 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
         }
         return;   // block-uniform: no barrier below is reached by only part of the block
     }
-    const uint32_t fr_of = lane / C, ch = lane % C;   // staging: frame within round, chunk
-    // The tile's header rows and the lane's own length / ingress ifindex are loaded at the top
-    // of each tile, with no register prefetch of the next tile: the other waves of the CU (16
-    // in the staged launch) hide the latency, and the prefetch's extra registers pushed the
-    // 12-wave kernel into scratch spills (measured 152 us against 121 us); pulling
+    // staging: the lane's frame within a round and its chunk, that chunk's byte offset from the
+    // tile's first frame, and the wave's rows
+    const uint32_t fr_of = lane / kBrChunks, ch = lane % kBrChunks;
+    const uint32_t voff = fr_of * (uint32_t)slot + 16u * ch;
+    uint32_t *const rows = s_hdr + wib * 64 * kBrRow;
+    // The tile's header rows and the lane's own length / ingress ifindex are loaded into
+    // registers once per tile, with no second register set for a tile further ahead: the other
+    // waves of the CU (16 in the staged launch) hide the latency, and the extra registers pushed
+    // the 12-wave kernel into scratch spills (measured 152 us against 121 us); pulling
     // the next tile into L2 with one dword load per frame was 8 % slower (its load sits in the
     // in-order vmcnt queue of the current tile, profiles/r02/br_ab/pf_lane_w16_ab_r02c1.log).
-    uint4 pre[C];
-    uint32_t pre_len = 0, pre_ifx = 0;
-    auto fetch = [&](uint64_t tt) {
-        if constexpr (WIN > 0) {
-#pragma unroll
-            for (int r = 0; r < C; ++r) {
-                uint64_t fi = tt * 64 + (uint64_t)(r * (64 / C)) + fr_of;
-                if (fi >= n) fi = n - 1;   // unconditional (counted vmcnt); masked at use
-                pre[r] = *reinterpret_cast<const uint4 *>(pkts + fi * slot + 16 * ch);
-            }
-        }
-        uint64_t fi = tt * 64 + lane;
-        if (fi >= n) fi = n - 1;
-        pre_len = lens[fi];
-        pre_ifx = ifidx[fi];
-    };
-    // HFV_BR_WB == 1: the same loads as buffer loads from a wave-uniform tile base (one lane
-    // offset for all C chunks; lanes past the batch read zeros instead of a clamped frame)
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    typedef uint32_t v2u __attribute__((ext_vector_type(2)));
-    const uint32_t voff = fr_of * (uint32_t)slot + 16u * ch;
-    auto fetch_buf = [&](uint64_t tt) {
-        // past the last tile: a zero-sized range (every load returns zeros, no memory access), so
-        // the loop can issue the next tile's loads unconditionally
+    BrTile pre;
+    pre.len = pre.ifx = 0;
+    // Issue tile tt's loads: buffer loads from a wave-uniform tile base (one lane offset for all
+    // chunks; lanes past the batch read zeros).  Past the last tile the range is empty, so the loop
+    // can issue the next tile's loads unconditionally and wait with a counted vmcnt.
+    // (A lambda: it needs eight of the kernel's values.)
+    auto fetch_tile = [&](uint64_t tt) {
         const uint64_t left = tt * 64 < n ? n - tt * 64 : 0;
         const uint32_t nf = left < 64 ? (uint32_t)left : 64u;
-        const __amdgpu_buffer_rsrc_t rs =
-            __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(pkts) + tt * 64 * slot, 0, (int)(nf * (uint32_t)slot), 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs = tile_rsrc(pkts, tt, nf, slot);
 #pragma unroll
-        for (int r = 0; r < C; ++r) {
-            // the whole offset in the VGPR: the bounds check does not cover soffset
-            const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(voff + r * (64 / C) * (uint32_t)slot), 0, 0);
-            pre[r] = make_uint4(v.x, v.y, v.z, v.w);
-        }
-        uint64_t fi = tt * 64 + lane;
-        if (fi >= n) fi = n - 1;
-        pre_len = lens[fi];
-        pre_ifx = ifidx[fi];
+        for (int r = 0; r < kBrChunks; ++r) pre.hdr[r] = load_chunk(rs, voff + r * kBrRound * (uint32_t)slot);
+        fetch_lane(lens, ifidx, n, lane, tt, pre);
     };
-    BrProf prof;
-    constexpr bool kEarly = WIN > 0 && HFV_BR_WB == 1;
-    constexpr bool kDyn = kEarly && HFV_BR_DYN;
-    // kDyn: this block's tiles [tb0, tb1), handed out by s_br_next (ntiles: nothing left)
+    // staged: this block's tiles [tb0, tb1)
     const uint64_t tb0 = ntiles * blockIdx.x / gridDim.x, tb1 = ntiles * (blockIdx.x + 1) / gridDim.x;
-    auto claim = [&]() -> uint64_t {
-        uint32_t g = 0;
-        if (lane == 0) g = __hip_atomic_fetch_add(&s_br_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const uint64_t tt = tb0 + __builtin_amdgcn_readfirstlane(g);
-        return tt < tb1 ? tt : ntiles;
-    };
-    if constexpr (kDyn) t = claim();
+    if constexpr (kStaged) t = claim_tile(lane, tb0, tb1, ntiles);
     uint64_t tnext = t + nwaves;
-    if constexpr (kEarly) {
-        if (t < ntiles) fetch_buf(t);
-        // (a builtin, so the waitcnt pass knows: the loop's vmcnt(C) assumes C younger stores)
+    if constexpr (kStaged) {
+        if (t < ntiles) fetch_tile(t);
+        // (a builtin, so the waitcnt pass knows: the loop's vmcnt(kBrChunks) assumes that many younger stores)
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) expcnt(7) lgkmcnt(15)
     }
-    for (; t < ntiles; t = kDyn ? tnext : t + nwaves) {
-        prof.start();
-        if constexpr (!kEarly) fetch(t);
-        if constexpr (kEarly) {
-            // the loads of this tile were issued at the end of the previous one, before its C
-            // write-back stores: wait for everything but those stores
-            __builtin_amdgcn_s_waitcnt(0x0F70 | C);   // vmcnt(C) expcnt(7) lgkmcnt(15)
-        }
-        if constexpr (WIN > 0) {
-            uint32_t *rows = s_hdr + wib * 64 * kBrRow;
+    for (; t < ntiles; t = kStaged ? tnext : t + nwaves) {
+        if constexpr (kStaged) {
+            // the loads of this tile were issued at the end of the previous one, before its
+            // write-back stores: wait for everything but those stores, then stage the rows
+            __builtin_amdgcn_s_waitcnt(0x0F70 | kBrChunks);   // vmcnt(kBrChunks) expcnt(7) lgkmcnt(15)
 #pragma unroll
-            for (int r = 0; r < C; ++r) {
-                uint32_t *d = rows + (r * (64 / C) + fr_of) * kBrRow + 4 * ch;
-                d[0] = pre[r].x; d[1] = pre[r].y; d[2] = pre[r].z; d[3] = pre[r].w;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            for (int r = 0; r < kBrChunks; ++r) put_chunk(row_chunk(rows, r * kBrRound + fr_of, ch), pre.hdr[r]);
+            wave_sync();
+        } else {
+            fetch_lane(lens, ifidx, n, lane, t, pre);
         }
-        const uint32_t len = pre_len, ifx = pre_ifx;
-        if constexpr (HFV_BR_PROF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        prof.mark(0);
+        const uint32_t len = pre.len, ifx = pre.ifx;
         uint64_t i = t * 64 + lane;
         uint32_t dirty = 0;
         if (i < n) {
@@ -975,75 +917,36 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
             k.len = (int)(len <= maxlen ? len : maxlen);
             k.lim = k.len < (int)window ? k.len : (int)window;
             k.ifindex = ifx;
-            if constexpr (kEarly && HFV_BR_EXT) {
-                // the SCION header's end by its HdrLen (sc + 5; sc after Ethernet, IPv4 with its
-                // IHL or IPv6, and UDP): a hint only, every read still checks its own bounds
-                const uint32_t proto = lds_u16_at(k, 12);
-                const int udp = proto == 0x0008u ? 14 + 4 * (int)(lds_u16_at(k, 14) & 0x0fu) : 54;
-                const int sc = udp + 8;
-                const int end = sc + 4 * (int)(reinterpret_cast<const uint8_t *>(s_hdr + k.row)[sc + 5 < WIN ? sc + 5 : 0]);
-                k.has_ext = k.lim > WIN && sc + 5 < WIN && end > WIN && (proto == 0x0008u || proto == 0xdd86u);
-                const uint64_t left = n - t * 64;
-                const uint32_t nf = left < 64 ? (uint32_t)left : 64u;
-                const __amdgpu_buffer_rsrc_t rx =
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(pkts) + t * 64 * slot, 0, (int)(nf * (uint32_t)slot), 0x00020000);
-                const v2u e = __builtin_amdgcn_raw_buffer_load_b64(rx, (int)(k.has_ext ? lane * (uint32_t)slot + WIN : 0x80000000u), 0, 0);
-                k.ext[0] = e.x; k.ext[1] = e.y;
-            }
-            br_frame<STATS>(k, i, &st->keys, action, verdict, egress, prof);
+            if constexpr (kStaged) load_ext(pkts, slot, n, lane, t, k);
+            br_frame<STATS>(k, i, &st->keys, action, verdict, egress);
             dirty = k.dirty;
         }
-        prof.mark(2);
-        if constexpr (WIN > 0) {
-            // write the rewritten 16-byte chunks back (WIN / 16 lanes per frame, each storing its
-            // chunk if the frame's lane wrote into it): untouched chunks stay clean in L2, so a
-            // frame whose changes lie in one 32-byte sector of a line costs that sector, not the line
-            uint32_t cmask[C];
+        if constexpr (kStaged) {
+            // Write-back of the rewritten 16-byte chunks (kBrChunks lanes per frame, each storing
+            // its chunk if the frame's lane wrote into it): untouched chunks stay clean in L2, so a
+            // frame whose changes lie in one 32-byte sector of a line costs that sector, not the line.
+            uint32_t cmask[kBrChunks];   // BrFrame::dirty of the frames this lane stores for
 #pragma unroll
-            for (int r = 0; r < C; ++r) cmask[r] = (uint32_t)__shfl((int)dirty, r * (64 / C) + (int)fr_of);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            const uint32_t *rows = s_hdr + wib * 64 * kBrRow;
-            if constexpr (HFV_BR_WB == 1) {
-                // the next tile's loads go to registers (the rows are read below, then restaged at
-                // the top of the next iteration), ahead of this tile's stores
-                tnext = kDyn ? claim() : t + nwaves;
-                fetch_buf(tnext);
-                const __amdgpu_buffer_rsrc_t rs =
-                    __builtin_amdgcn_make_buffer_rsrc(out + t * 64 * slot, 0, (int)(64u * (uint32_t)slot), 0x00020000);
+            for (int r = 0; r < kBrChunks; ++r) cmask[r] = (uint32_t)__shfl((int)dirty, r * kBrRound + (int)fr_of);
+            wave_sync();
+            // The next tile's loads go to registers (the rows are read below, then restaged at the
+            // top of the next iteration), ahead of this tile's stores: vmcnt retires in order, so
+            // stores issued first would make the wait for the loads also wait for the stores'
+            // acknowledgement ("Write-back order").
+            tnext = claim_tile(lane, tb0, tb1, ntiles);
+            fetch_tile(tnext);
+            // Lanes without a change address past the buffer (dropped by the bounds check: no
+            // branch, a fixed count of kBrChunks stores, which the vmcnt above relies on).
+            const __amdgpu_buffer_rsrc_t rs = tile_rsrc(out, t, 64u, slot);
 #pragma unroll
-                for (int r = 0; r < C; ++r) {
-                    const uint32_t fr = r * (64 / C) + fr_of;
-                    const uint32_t *q = rows + fr * kBrRow + 4 * ch;
-                    const v4u q4 = v4u{q[0], q[1], q[2], q[3]};
-                    const uint32_t off = ((cmask[r] >> ch) & 1u) ? voff + r * (64 / C) * (uint32_t)slot : 0x80000000u;
-                    __builtin_amdgcn_raw_buffer_store_b128(q4, rs, (int)off, 0, 0);
-                }
-            } else if constexpr (HFV_BR_WB == 0) {
-#pragma unroll
-                for (int r = 0; r < C; ++r) {
-                    uint32_t fr = r * (64 / C) + fr_of;
-                    if ((cmask[r] >> ch) & 1u) {
-                        const uint32_t *q = rows + fr * kBrRow + 4 * ch;
-                        *reinterpret_cast<uint4 *>(out + (t * 64 + fr) * slot + 16 * ch) = make_uint4(q[0], q[1], q[2], q[3]);
-                    }
-                }
+            for (int r = 0; r < kBrChunks; ++r) {
+                const v4u q4 = get_chunk(row_chunk(rows, r * kBrRound + fr_of, ch));
+                const uint32_t off = ((cmask[r] >> ch) & 1u) ? voff + r * kBrRound * (uint32_t)slot : kPastBuffer;
+                __builtin_amdgcn_raw_buffer_store_b128(q4, rs, (int)off, 0, 0);
             }
+            wave_sync();   // every lane is done with the rows before they are restaged
         }
-        if constexpr (WIN > 0) {   // every lane is done with the rows before they are restaged
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        if constexpr (HFV_BR_PROF) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        prof.mark(3);
-        prof.c[4] += 1;
     }
-#if HFV_BR_PROF
-    if (lane == 0)
-        for (int q = 0; q < 5; ++q) atomicAdd(&g_br_prof[q], (unsigned long long)prof.c[q]);
-#endif
     if constexpr (STATS) {
         __syncthreads();
         for (uint32_t e = threadIdx.x; e < HFV_BR_STATS_IFINDEX * 2 * HFV_BR_COUNTERS; e += BLOCK) {
@@ -1052,16 +955,6 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
         }
     }
 }
-
-#if HFV_BR_PROF
-// diagnostics: the phase counters of the kernels run since the last call (then cleared)
-extern "C" int hfv_debug_br_prof(unsigned long long out[8])
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_br_prof), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    static const unsigned long long zero[8] = {};
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_br_prof), zero, sizeof zero) == hipSuccess ? 0 : -1;
-}
-#endif
 
 int launch_br_process(const LaunchGeom &g, const DevState *st, uint8_t *pkts, size_t slot, uint32_t maxlen,
                       uint32_t window, const uint16_t *len, const uint32_t *ingress_ifindex, size_t n,
@@ -1090,7 +983,6 @@ int launch_br_process(const LaunchGeom &g, const DevState *st, uint8_t *pkts, si
         block = 1024;
         k = stats ? k_br_process<1024, true, 0> : k_br_process<1024, false, 0>;
     }
-#if HFV_BR_STATS32
     // 32-bit block counters: split a launch whose blocks could count 2^32 bytes of one kind
     // (a block's frames x the largest length); every launch adds into the same counters
     if (stats) {
@@ -1111,7 +1003,6 @@ int launch_br_process(const LaunchGeom &g, const DevState *st, uint8_t *pkts, si
             return 0;
         }
     }
-#endif
     const uint64_t tiles = (n + 63) / 64, cap = (uint64_t)g.num_cus;   // one block per CU at most
     unsigned grid = (unsigned)(tiles < cap ? (tiles ? tiles : 1) : cap);
     if (g.br_grid_cap && g.br_grid_cap < grid) grid = g.br_grid_cap;   // test build only

@@ -37,6 +37,7 @@
 
 #include "hfv_frame_parse.h"
 #include "hfv_internal.h"
+#include "hfv_wave_sync.h"
 
 // HFV_MUT_WINEDGE = 5 (`make winedge`, see hfv_br_kernel.hip): u32 takes a field across the window
 // end from the row and its zeroed pad dword.  0 (the default, every product build): as written.
@@ -133,9 +134,7 @@ __global__ __launch_bounds__(kFrWaves * 64) void k_extract_records(const uint8_t
             d[0] = pre[r].x; d[1] = pre[r].y; d[2] = pre[r].z; d[3] = pre[r].w;
         }
         rows[lane * kFrRow + kFrWin / 4] = 0u;   // the lane's pad dword: read (and shifted out) by u32(124)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_sync();
     }
     if (lane >= nf) return;
     const FrameReader<WIN> rd = {rows + lane * kFrRow, frames + i * slot};

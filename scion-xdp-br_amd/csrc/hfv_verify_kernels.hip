@@ -203,17 +203,9 @@ __device__ __forceinline__ RecWords batch_load(const BatchTile &b, uint32_t g, u
     return load_tile<true>(b, g - b.lo, lane, inf_off, hf_off);
 }
 
-// DEPTH: tiles whose record loads are in flight ahead of the one being verified (1: the next
-// tile's, as k_verify_records; 2: the next two -- HFV_BATCH_DEPTH, an A/B build switch).  Every
-// load is issued unconditionally (a claim past the block's range re-reads its last tile), so the
-// waitcnt pass keeps a counted vmcnt for the tiles still ahead instead of a vmcnt(0).
-#ifndef HFV_BATCH_DEPTH
-#define HFV_BATCH_DEPTH 1
-#endif
-// HFV_BATCH_PIN: each AES round's issue order pinned (16 addresses, 16 reads, 8 xor3; round_full)
-#ifndef HFV_BATCH_PIN
-#define HFV_BATCH_PIN 1
-#endif
+// The next tile's record loads are in flight while the current one is verified, as in
+// k_verify_records.  Every load is issued unconditionally (a claim past the block's range re-reads
+// its last tile), so the waitcnt pass keeps a counted vmcnt for the tile ahead instead of a vmcnt(0).
 // HFV_MUT_TILEDEAL=N (make tiledeal; 0: the product): one deliberately wrong step in the tile dealing
 // of k_verify_batches, which tests/test_gpu_tile_deal.py must fail on.  Every mutant only masks
 // wrongly, or skips a store it owes to a bitmap: none moves a load or a store.
@@ -224,10 +216,9 @@ __device__ __forceinline__ RecWords batch_load(const BatchTile &b, uint32_t g, u
 #ifndef HFV_MUT_TILEDEAL
 #define HFV_MUT_TILEDEAL 0
 #endif
-template <int KEYSEL, int DEPTH>
+template <int KEYSEL>
 __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
 {
-    static_assert(DEPTH == 1 || DEPTH == 2, "prefetch depth");
     const BArgs a = (BArgs)__builtin_amdgcn_kernarg_segment_ptr();
     (void)args;
     const uint32_t lane = threadIdx.x & 63;
@@ -259,11 +250,11 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
         if (lane == 0) c = atomicAdd(&s_next_tile, 1u);
         return b0 + wave_uniform(c);
     };
-    // Record buffers: the loop is unrolled DEPTH + 1 times over DEPTH + 1 fixed register slots, slot
-    // u verified in step u while the loads of the tile DEPTH claims ahead land in the slot step u - 1
-    // just verified -- so no loop-carried register copy (which would wait for the loads it copies,
-    // a vmcnt(0) at the latch) stands between a tile's loads and its use.
-    constexpr int S = DEPTH + 1;
+    // Record buffers: the loop is unrolled twice over two fixed register slots, slot u verified in
+    // step u while the loads of the next claim land in the other slot, which step u - 1 just
+    // verified -- so no loop-carried register copy (which would wait for the loads it copies, a
+    // vmcnt(0) at the latch) stands between a tile's loads and its use.
+    constexpr int S = 2;
     RecWords buf[S];
     BatchTile bt[S];
     uint32_t gg[S];
@@ -272,13 +263,6 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
     bt[0].j = ~0u;          // batch_map starts its search at batch 0
     batch_map(a, at(gg[0]), bt[0]);
     buf[0] = batch_load(bt[0], at(gg[0]), lane, inf_off, hf_off);
-#pragma unroll
-    for (int d = 1; d < DEPTH; ++d) {
-        gg[d] = claim();
-        bt[d] = bt[d - 1];
-        batch_map(a, at(gg[d]), bt[d]);
-        buf[d] = batch_load(bt[d], at(gg[d]), lane, inf_off, hf_off);
-    }
     fill_block<KEYSEL>(a->pro.t0, a->tab, kBlock);
     __syncthreads();
     const Lane l = lane_bases();
@@ -298,9 +282,9 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
     for (;;) {
 #pragma unroll
         for (int u = 0; u < S; ++u) {
-            const int in_slot = (u + DEPTH) % S, prev = (u + DEPTH - 1) % S;   // the free slot, the newest mapped
+            const int in_slot = (u + 1) % S;   // the free slot; slot u holds the newest mapped batch
             gg[in_slot] = claim();
-            bt[in_slot] = bt[prev];
+            bt[in_slot] = bt[u];
             batch_map(a, at(gg[in_slot]), bt[in_slot]);
             buf[in_slot] = batch_load(bt[in_slot], at(gg[in_slot]), lane, inf_off, hf_off);
             const uint64_t rec = (uint64_t)(gg[u] - bt[u].lo) * 64 + lane;
@@ -309,7 +293,7 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
 #else
             const uint64_t n_own = bt[u].n;
 #endif
-            const uint64_t ballot = verify_tile<KEYSEL, HFV_BATCH_PIN != 0>(buf[u], rec < n_own, l, &ukey);
+            const uint64_t ballot = verify_tile<KEYSEL, true>(buf[u], rec < n_own, l, &ukey);
             if (lane == stashed) {
                 st_word = ballot;
                 st_addr = bt[u].bits + (uint64_t)(gg[u] - bt[u].lo) * 8;
@@ -347,8 +331,7 @@ done:
 int launch_verify_batches(const LaunchGeom &g, int keysel, const BatchArgs &args, void *stream, void *ev_start,
                           void *ev_stop)
 {
-    auto k = keysel == HFV_KEYSEL_IFID ? k_verify_batches<HFV_KEYSEL_IFID, HFV_BATCH_DEPTH>
-                                       : k_verify_batches<HFV_KEYSEL_ZERO, HFV_BATCH_DEPTH>;
+    auto k = keysel == HFV_KEYSEL_IFID ? k_verify_batches<HFV_KEYSEL_IFID> : k_verify_batches<HFV_KEYSEL_ZERO>;
     // one block per CU, but no more blocks than tiles: every block owns at least one tile
     uint64_t blocks = args.total;
     if (blocks > (uint64_t)g.num_cus) blocks = (uint64_t)g.num_cus;

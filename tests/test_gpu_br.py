@@ -226,7 +226,7 @@ def test_bench_batch_full_size_bit_exact(gpu_ctx, hf_check):
 
 
 def test_split_launch_counters(request, gpu_ctx):
-    """The block counters are 32-bit in LDS (HFV_BR_STATS32); a launch whose blocks could count
+    """The block counters are 32-bit in LDS (BrCount in hfv_br_kernel.hip); a launch whose blocks could count
     2^32 bytes is split into pieces that add into the same 64-bit counters.  Forced here with a
     small piece size (hfv_debug_br_split): a ragged 2^14 + 37-frame fuzz batch in pieces of 1000
     frames must give the oracle's frames, outputs and counters exactly."""
