@@ -111,6 +111,48 @@ __device__ __forceinline__ void fill_ttab_karg(P t0, uint32_t wave, uint32_t nw)
     }
 }
 
+// The same fill in two calls (ttab_karg_load, then ttab_karg_store), for a kernel that puts other
+// work between the T0 loads and the LDS writes that wait for them (k_verify_batches).
+template <int TAB>
+struct TtabFill {
+    static constexpr uint32_t kChunks = (TAB == 4 ? 131072 : 65536) / 1024;
+    static constexpr int kMax = (int)((kChunks + 14) / 15);   // at least 15 filling waves
+    uint32_t v[kMax];
+};
+
+template <int TAB, class P>
+__device__ __forceinline__ void ttab_karg_load(P t0, uint32_t wave, uint32_t nw, TtabFill<TAB> &f)
+{
+    constexpr uint32_t kChunks = TtabFill<TAB>::kChunks;
+    const uint32_t lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < TtabFill<TAB>::kMax; ++k) {
+        const uint32_t c = wave + k * nw;
+        const uint32_t e = (c << 3) + (lane >> 3);   // 128-byte run of table t at index x
+        f.v[k] = c < kChunks ? t0[(e >> 1) & 255u] : 0u;
+    }
+}
+
+template <int TAB>
+__device__ __forceinline__ void ttab_karg_store(uint32_t wave, uint32_t nw, const TtabFill<TAB> &f)
+{
+    constexpr uint32_t kChunks = TtabFill<TAB>::kChunks;
+    const uint32_t lane = threadIdx.x & 63;
+    char *lds = TAB == 4 ? reinterpret_cast<char *>(s_tab128) : reinterpret_cast<char *>(s_tab64);
+    const uint32_t *v = f.v;
+#pragma unroll
+    for (int k = 0; k < TtabFill<TAB>::kMax; ++k) {
+        const uint32_t c = wave + k * nw;
+        if (c < kChunks) {
+            const uint32_t e = (c << 3) + (lane >> 3);
+            const uint32_t t = (e & 1u) | (((e >> 9) & 1u) << 1);
+            const uint32_t x = t ? __builtin_amdgcn_alignbit(v[k], v[k], 32 - 8 * t) : v[k];
+            *reinterpret_cast<uint4 *>(lds + c * 1024 + lane * 16) = make_uint4(x, x, x, x);
+        }
+    }
+}
+
+
 // nthr: the block's threads 0..nthr-1 share the copy (0: all of them)
 __device__ __forceinline__ void fill_keys(const DevKeyTable *tab, uint32_t nthr = 0)
 {

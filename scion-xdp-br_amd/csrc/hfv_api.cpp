@@ -335,7 +335,8 @@ static int verify_records(hfv_ctx *ctx, const void *recs, size_t stride, size_t 
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
-    return with_tables(ctx, (hipStream_t)stream, "verify_records launch", [&](DevState *ds) {
+    const bool reader = launch_reads_tables(ctx->keysel);
+    return with_tables(ctx, (hipStream_t)stream, "verify_records launch", reader, [&](DevState *ds) {
         return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, (const uint8_t *)recs,
                                      stride, n, ctx->inf_off, ctx->hf_off, pass_bits, stream, ev0, ev1);
     });
@@ -383,7 +384,8 @@ static int batches_launch(hfv_ctx *ctx, const struct hfv_batch *b, size_t count,
     while (last > 0 && b[last - 1].n == 0) --last;
     // the block finish stamps are atomic maxima: cleared before timed launches (outside the events)
     if (ev0) HIP_TRY(hipMemsetAsync(ctx->bat_clk + 4 + kBatchStampBlocks, 0, kBatchStampBlocks * sizeof(uint64_t), st));
-    return with_tables(ctx, st, "verify_batches launch", [&](DevState *ds) {
+    const bool reader = launch_reads_tables(ctx->keysel);
+    return with_tables(ctx, st, "verify_batches launch", reader, [&](DevState *ds) {
         if (last == 0) return (int)hipSuccess;   // nothing to launch: the tables are published all the same
         BatchArgs a;
         memset(&a, 0, sizeof a);
@@ -410,7 +412,7 @@ static int batches_launch(hfv_ctx *ctx, const struct hfv_batch *b, size_t count,
             const bool fin = i >= last;
             int e = launch_verify_batches(batch_geom(ctx), ctx->keysel, a, st, ev0, fin ? ev1 : nullptr);
             if (e != hipSuccess || fin) return e;   // with_tables notes the last launch
-            note_reader(ctx, st);
+            if (reader) note_reader(ctx, st);
             ev0 = nullptr;
         }
     });

@@ -154,11 +154,12 @@ int svc_quiesce(hfv_ctx *ctx);
     } while (0)
 
 // hfv_publish.cpp.  after_launch turns a launcher's hipError_t into the call's result and notes
-// `st` as a reader of the table publish_keys returned (note_reader).
-int publish_keys(hfv_ctx *ctx, hipStream_t st, DevState **out);
+// `st` as a reader of the table publish_keys returned (note_reader).  reader: the launch's kernel
+// dereferences the DevState it is given (launch_reads_tables below; true for every other launch).
+int publish_keys(hfv_ctx *ctx, hipStream_t st, DevState **out, bool reader = true);
 void note_reader(hfv_ctx *ctx, hipStream_t st);
 bool own_stream(const hfv_ctx *ctx, hipStream_t st);
-int after_launch(hfv_ctx *ctx, hipStream_t st, int err, const char *what);
+int after_launch(hfv_ctx *ctx, hipStream_t st, int err, const char *what, bool reader = true);
 
 // hfv_api.cpp.  What every call taking records checks of them: null buffers, 8-byte alignment of
 // records, stride and bitmap, the stride against the ctx's record layout (a call's own limits stay with it).
@@ -184,13 +185,29 @@ static inline int fail_batch(int rc, size_t i)
     return fail(rc, "batch %zu: %s", i, why);
 }
 
+// Does the kernel of a record or batch-list verify launch (launch_verify_records,
+// launch_verify_batches) under `keysel` dereference the DevState it is launched with?  Under
+// KEYSEL_ZERO, k_verify_batches<ZERO> and k_verify_records<ZERO, *> take T0 and slot 0's key rows
+// from their kernel arguments (KeyPrologue) and fill_block never touches `tab`, so such a launch
+// is no reader of a device table: it neither waits for a publish copy pending on another stream
+// nor leaves a fence event for the next publish to wait on.  THIS MUST TRACK WHAT THE KERNELS
+// READ: a KEYSEL_ZERO verify kernel that starts reading the table has to make this true again.
+// Every other launch of the library reads its DevState and goes through with_tables as a reader.
+static inline bool launch_reads_tables(int keysel) { return keysel != HFV_KEYSEL_ZERO; }
+
 // One launch (or several) with the published tables: publish, launch(ds) -> hipError_t as int,
-// then note the stream as a reader of the table it launched with.
+// then note the stream as a reader of the table it launched with (reader = false: see above).
+template <class Launch>
+static inline int with_tables(hfv_ctx *ctx, hipStream_t st, const char *what, bool reader, Launch launch)
+{
+    DevState *ds;
+    int rc = publish_keys(ctx, st, &ds, reader);
+    if (rc) return rc;
+    return after_launch(ctx, st, launch(ds), what, reader);
+}
+
 template <class Launch>
 static inline int with_tables(hfv_ctx *ctx, hipStream_t st, const char *what, Launch launch)
 {
-    DevState *ds;
-    int rc = publish_keys(ctx, st, &ds);
-    if (rc) return rc;
-    return after_launch(ctx, st, launch(ds), what);
+    return with_tables(ctx, st, what, true, launch);
 }

@@ -479,7 +479,8 @@ static int verify_records_zero_copy(hfv_ctx *ctx, const uint8_t *drecs, size_t s
         }
         dbits = (uint64_t *)ctx->zc_meta;
     }
-    int rc = with_tables(ctx, st, "verify_records launch (zero-copy)", [&](DevState *ds) {
+    const bool reader = launch_reads_tables(ctx->keysel);
+    int rc = with_tables(ctx, st, "verify_records launch (zero-copy)", reader, [&](DevState *ds) {
         return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, drecs, stride, n,
                                      ctx->inf_off, ctx->hf_off, dbits, st, nullptr, nullptr, /*interleaved=*/true);
     });
@@ -537,7 +538,7 @@ int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_
         size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
         gather_hf(ctx->h_pin[slot], (const uint8_t *)recs + first * stride, stride, ctx->inf_off, ctx->hf_off, cnt);
         HIP_TRY(hipMemcpyAsync(ctx->d_rec[slot], ctx->h_pin[slot], cnt * kHostRec, hipMemcpyHostToDevice, st));
-        rc = with_tables(ctx, st, "verify_records launch", [&](DevState *ds) {
+        rc = with_tables(ctx, st, "verify_records launch", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
             return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, ctx->d_rec[slot],
                                          kHostRec, cnt, 0, 8, ctx->d_bits[slot], st);
         });

@@ -37,8 +37,11 @@ static constexpr uint32_t g_pub_delay_us = 0;
 
 // Make the shadow table visible to work enqueued next on `st` -- and, once the copy is queued,
 // to work on any other stream (which waits for the copy until it has been seen complete);
-// returns the table to use.
-int publish_keys(hfv_ctx *ctx, hipStream_t st, DevState **out)
+// returns the table to use.  reader = false (launch_reads_tables): the launch that follows reads no
+// device table, so `st` does not wait for a pending copy made on another stream; everything else
+// -- the pick-up of attached maps, the rebuild of the staging image (the launch's key prologue is
+// cut from it), the device copy and the fences of that copy -- is done all the same.
+int publish_keys(hfv_ctx *ctx, hipStream_t st, DevState **out, bool reader)
 {
     if (ctx->keymap) {   // pick up updates other processes made to the pinned map
         uint32_t seq = keymap_seq(ctx->keymap);
@@ -109,7 +112,7 @@ int publish_keys(hfv_ctx *ctx, hipStream_t st, DevState **out)
         ctx->active = next;
         ctx->dirty = false;
         ctx->pub_pending = true;
-    } else if (HFV_PUB_FENCE && ctx->pub_pending) {
+    } else if (HFV_PUB_FENCE && ctx->pub_pending && reader) {
         // The copy into dev_tab[active] was enqueued on the stream that published it; work on any
         // other stream must not read the table before that copy lands.  (Round 2 skipped this: the
         // config-5 loop published on its chunk-0 stream and launched chunk 1 on a second stream,
@@ -144,10 +147,10 @@ void note_reader(hfv_ctx *ctx, hipStream_t st)
     if (!own_stream(ctx, st) && hipEventRecord(ctx->reader_ev[a][r], st) != hipSuccess) ctx->readers_overflow[a] = true;
 }
 
-int after_launch(hfv_ctx *ctx, hipStream_t st, int err, const char *what)
+int after_launch(hfv_ctx *ctx, hipStream_t st, int err, const char *what, bool reader)
 {
     if (err != hipSuccess) return hip_fail((hipError_t)err, what);
-    note_reader(ctx, st);
+    if (reader) note_reader(ctx, st);
     return 0;
 }
 

@@ -112,6 +112,15 @@ __device__ __forceinline__ void fill_block(P t0, const DevKeyTable *tab, uint32_
 constexpr int kBlock = 1024;
 constexpr uint32_t kWaves = kBlock / 64;
 
+// fill_block's second half for a whole block of kBlock threads whose T0 words are already
+// requested (ttab_karg_load<4>(t0, wave, kWaves, f)): the LDS writes, and config 3's key rows.
+template <int KEYSEL>
+__device__ __forceinline__ void fill_block_store(const TtabFill<4> &f, const DevKeyTable *tab)
+{
+    ttab_karg_store<4>(threadIdx.x >> 6, kWaves, f);
+    if constexpr (KEYSEL == HFV_KEYSEL_IFID) fill_keys5(tab, kBlock);
+}
+
 // host: blocks for n records in tiles of 64, one wave per tile, at most per_cu blocks per CU
 static inline unsigned grid_for(uint64_t n, int block, int num_cus, int per_cu)
 {

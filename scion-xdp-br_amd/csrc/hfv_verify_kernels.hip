@@ -164,10 +164,12 @@ __global__ __launch_bounds__(kBlock) void k_verify_records(const DevKeyTable *__
 // space, its waves claiming tiles from an LDS counter as k_verify_records does.  A block's
 // range spans one or two batches, so a wave changes batch about once per block range: the
 // batch's descriptor sits in SGPRs, read from the kernel arguments (scalar loads) only when a
-// claim leaves it.  Against the resident service (k_verify_service) this launch has no relay
-// wave, no completion protocol and no system-scope verdict stores (the launch is stream
-// ordered: the kernel's end publishes the bitmaps), and it pays the table fill once for all
-// of its batches instead of once per batch as a launch per batch does.
+// claim leaves it: the batch of a wave's first tile is found by binary search over cum[]
+// (batch_find), every later one by a forward step from the current batch (batch_map).  Against
+// the resident service (k_verify_service) this launch has no relay wave, no completion protocol
+// and no system-scope verdict stores (the launch is stream ordered: the kernel's end publishes the
+// bitmaps), and it pays the table fill once for all of its batches instead of once per batch as a
+// launch per batch does.
 typedef const __attribute__((address_space(4))) BatchArgs *BArgs;
 
 struct BatchTile {   // the wave's current batch (wave-uniform)
@@ -194,6 +196,26 @@ __device__ __forceinline__ void batch_map(BArgs a, uint32_t g, BatchTile &b)
     uint32_t j = b.j + 1;
     while (g >= a->cum[j + 1]) ++j;
     batch_enter(a, j, b);
+}
+
+// global tile g -> the j with cum[j] <= g < cum[j + 1] (g < a->total), by binary search: at most
+// log2(kBatchMax) + 1 dependent scalar loads, wherever in the list the tile lies.  cum[] is strictly
+// increasing (the host drops empty batches).  For a wave's first tile only: batch_map's forward
+// step from batch 0 costs a block whose range starts in batch j as many load round trips as j,
+// ahead of its first record loads.
+__device__ __forceinline__ uint32_t batch_find(BArgs a, uint32_t nb, uint32_t g)
+{
+    uint32_t lo = 0, len = nb;   // cum[lo] <= g < cum[lo + len]
+    while (len > 1) {
+        const uint32_t half = len >> 1;
+        if (g >= a->cum[lo + half]) {
+            lo += half;
+            len -= half;
+        } else {
+            len = half;
+        }
+    }
+    return lo;
 }
 
 // global tile g of batch b (non-temporal: the records are read once per launch)
@@ -223,13 +245,12 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
     (void)args;
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wv = wave_uniform(threadIdx.x / 64);
-    const uint32_t total = a->total;
+    const uint32_t total = a->total, nb = a->nb;
     const uint32_t b0 = (uint32_t)((uint64_t)total * blockIdx.x / gridDim.x);
     const uint32_t b1 = (uint32_t)((uint64_t)total * (blockIdx.x + 1) / gridDim.x);
     if (b1 == b0) return;   // (the launcher gives every block at least one tile)
     const uint32_t last = b1 - 1;
     const uint32_t inf_off = a->inf_off, hf_off = a->hf_off;
-    UniformKey ukey(a->pro.key0, a->pro.key0_ok);
     // diagnostics, stored before the first record loads are issued (a store issued after them would
     // make the loop's first reuse of its data registers wait for every load ahead of it: vmcnt(0))
     if (threadIdx.x == 0 && a->clk) {
@@ -258,12 +279,22 @@ __global__ __launch_bounds__(kBlock) void k_verify_batches(const BatchArgs args)
     RecWords buf[S];
     BatchTile bt[S];
     uint32_t gg[S];
-    gg[0] = b0 + wv;        // the wave's first tile (static), its loads in flight while the tables are written
-    bt[0].hi = 0;
-    bt[0].j = ~0u;          // batch_map starts its search at batch 0
-    batch_map(a, at(gg[0]), bt[0]);
+    // The prologue's two memory chains start together: the T0 loads of the table fill are issued
+    // first, then the wave's first tile (static) is found in cum[] and its record loads are issued,
+    // and only then the fill's LDS writes wait for T0 (a counted vmcnt: the record loads are younger
+    // and stay in flight while the tables are written).  The slot-0 key rows are asked for ahead
+    // of the search as well: named behind the record loads, the compiler sinks their 48 scalar
+    // loads to the first use, behind the barrier, one more serial round trip to the kernel
+    // arguments per block.  The fill takes threadIdx.x >> 6 for the wave, as fill_block does: the
+    // compiler knows its bound and emits four unconditional T0 loads, where the scalar copy wv
+    // gave eight behind scalar branches (one-batch launches 16.4 -> 17.4 us).
+    TtabFill<4> t0w;
+    ttab_karg_load<4>(a->pro.t0, threadIdx.x >> 6, kWaves, t0w);
+    gg[0] = b0 + wv;
+    UniformKey ukey(a->pro.key0, a->pro.key0_ok);
+    batch_enter(a, batch_find(a, nb, at(gg[0])), bt[0]);
     buf[0] = batch_load(bt[0], at(gg[0]), lane, inf_off, hf_off);
-    fill_block<KEYSEL>(a->pro.t0, a->tab, kBlock);
+    fill_block_store<KEYSEL>(t0w, a->tab);
     __syncthreads();
     const Lane l = lane_bases();
     // verdict words wait in a per-wave stash (lane k: the wave's k-th tile, with its own bitmap
