@@ -40,6 +40,13 @@
 #ifndef HFV_MUT_WINEDGE
 #define HFV_MUT_WINEDGE 0
 #endif
+// HFV_MUT_CSUM = 1..5 (`make csumedge`): one wrong checksum rule each in fold_checksum / mut_checksum
+// (1 a third fold, 2 the zero test on the low 16 bits, 3 ~check taken at 16 bits, 4 the sum cut to
+// 32 bits, 5 the RFC 1624 one's-complement update), for the libraries tests/test_gpu_br_csum.py
+// must fail on.  0 (the default, every product build): the reference's rule.
+#ifndef HFV_MUT_CSUM
+#define HFV_MUT_CSUM 0
+#endif
 
 namespace hfv {
 
@@ -512,14 +519,40 @@ __device__ __forceinline__ int ip_route(const BrFrame &k)
 }
 
 // ---- rewrite.h -------------------------------------------------------------------------------
+// FOLD_CHECKSUM (rewrite.h:35-40): two folds only, which do not reduce a 64-bit sum, and a zero test
+// on all 64 bits after ~, which no sum meets; the results are the reference's for every residual,
+// wrapped ("negative") ones included, only like this (tests/br_csum.py has the rule in integers).
 __device__ __forceinline__ uint32_t fold_checksum(uint64_t c)
 {
     c = (c & 0xffffu) + (c >> 16);
     c = (c & 0xffffu) + (c >> 16);
+#if HFV_MUT_CSUM == 1
+    c = (c & 0xffffu) + (c >> 16);
+#endif
     c = ~c;
+#if HFV_MUT_CSUM == 2
+    if ((c & 0xffffu) == 0) c = 0xffff;
+#else
     if (c == 0) c = 0xffff;
+#endif
     return (uint32_t)(c & 0xffffu);
 }
+
+// The stored check field from cs = ~check + residual + 1 (rewrite.h:64-65, 115-116; `check` is a u16
+// promoted to int, so ~check converts to u64 as 2^64 - 1 - check).  The mutants 3..5 start again
+// from check and residual.
+#if HFV_MUT_CSUM >= 3
+__device__ __forceinline__ uint32_t mut_checksum(uint32_t check, uint64_t res)
+{
+    if (HFV_MUT_CSUM == 3) return fold_checksum((uint64_t)(~check & 0xffffu) + res + 1);
+    if (HFV_MUT_CSUM == 4) return fold_checksum((uint32_t)(~(uint64_t)check + res + 1));
+    const int64_t d = (int64_t)(res - (uint64_t)check);
+    return 0xffffu - (uint32_t)(((d - 1) % 65535 + 65535) % 65535 + 1);
+}
+#define HFV_CHECK_FIELD(cs, check, res) ((void)(cs), mut_checksum(check, res))
+#else
+#define HFV_CHECK_FIELD(cs, check, res) fold_checksum(cs)
+#endif
 
 // rewrite / rewrite_scion_path (rewrite.h:35-146).  The BPF code subtracts every original
 // field from its u64 checksum residuals as it parses them and adds the new values here; the
@@ -560,7 +593,7 @@ __device__ __forceinline__ void rewrite(BrFrame &k)
         wr8(k, k.ip + 8, nttl);
         const uint64_t ip_res = c + (uint64_t)nttl - (uint64_t)ottl;
         uint64_t cs = ~(uint64_t)rd16(k, k.ip + 10) + ip_res + 1;
-        wr16(k, k.ip + 10, fold_checksum(cs));
+        wr16(k, k.ip + 10, HFV_CHECK_FIELD(cs, rd16(k, k.ip + 10), ip_res));
     } else {
         const bool put = k.ip + 24 + 16 < k.len && k.ip + 8 + 16 < k.len;
 #pragma unroll
@@ -602,7 +635,7 @@ __device__ __forceinline__ void rewrite(BrFrame &k)
         }
     }
     uint64_t cs = ~(uint64_t)rd16(k, k.udp + 6) + udp_res + 1;
-    wr16(k, k.udp + 6, fold_checksum(cs));
+    wr16(k, k.udp + 6, HFV_CHECK_FIELD(cs, rd16(k, k.udp + 6), udp_res));
 }
 
 // The rewrite's only stores into the SCION path after PathMeta are the SegIDs at INF+2 and, on a

@@ -167,9 +167,9 @@ def test_router_tile_mixing(gpu_ctx, order, v6):
 
 # ---- hfv_br_process_host ------------------------------------------------------------------------
 
-def check_host_path(ctx, v6, frames, lens, ifidx, want, want_frames, window, register=False):
+def check_host_path(ctx, v6, frames, lens, ifidx, want, want_frames, window, register=False, cfg=None):
     n = len(frames)
-    setup_router(ctx, T.br_config("br1", v6))
+    setup_router(ctx, T.br_config("br1", v6) if cfg is None else cfg)
     got = hfv.host_array(frames.shape, np.uint8) if register else np.empty_like(frames)
     got[:] = frames
     a, v, e = np.full(n, FILL_OUT, np.uint8), np.full(n, FILL_OUT, np.uint8), np.full(n, -77, np.int32)
