@@ -587,6 +587,16 @@ int hfv_debug_service_weights(hfv_ctx *ctx, uint32_t out[9])
     return 0;
 }
 
+// Diagnostic (not part of include/scion_hfv.h): the weights the running / last service grid was
+// launched with (svc_w_used, what svc_balance reads), in the same order.
+int hfv_debug_service_weights_used(hfv_ctx *ctx, uint32_t out[9])
+{
+    if (!ctx || !out) return fail(-EINVAL, "bad argument");
+    for (int x = 0; x < 8; ++x) out[x] = ctx->svc_w_used.w[x];
+    out[8] = ctx->svc_w_used.w0;
+    return 0;
+}
+
 // Diagnostic (not part of include/scion_hfv.h): out[i] = s_memrealtime (100 MHz) when block
 // 0 loaded ring slot i's descriptor from the mirror (i < kSvcRing; inline batches are not
 // loaded); out[kSvcRing .. kSvcRing + 3] = block 0 wave 0's s_memtime and s_memrealtime at its
@@ -678,6 +688,20 @@ int hfv_debug_service_call_ns(hfv_ctx *ctx, uint64_t out[5])
 int hfv_debug_relay_delay(uint32_t us)
 {
     g_svc_relay_delay_us = us > 100000u ? 100000u : us;
+    return 0;
+}
+
+// Test hook (test build only): the block weights the next service grid will use, in the order
+// hfv_debug_service_weights reports them (w[0..7] per XCD, then block 0's).  Only values
+// svc_balance can produce: each inside its clamp [kSvcWeightUnit / 2, 2 kSvcWeightUnit].
+int hfv_debug_service_set_weights(hfv_ctx *ctx, const uint32_t w[9])
+{
+    if (!ctx || !w) return fail(-EINVAL, "bad argument");
+    for (int x = 0; x < 9; ++x)
+        if (w[x] < kSvcWeightUnit / 2 || w[x] > kSvcWeightUnit * 2)
+            return fail(-EINVAL, "weight %d = %u outside [%u, %u]", x, w[x], kSvcWeightUnit / 2, kSvcWeightUnit * 2);
+    for (int x = 0; x < 8; ++x) ctx->svc_w.w[x] = w[x];
+    ctx->svc_w.w0 = w[8];
     return 0;
 }
 #endif

@@ -436,6 +436,21 @@ __device__ __forceinline__ SvcClaim svc_map(KArgs a, uint32_t lane, uint32_t g, 
     }
 }
 
+// HFV_MUT_SVCDEAL=N (make svcdeal; 0: the product): one deliberately wrong step in the tile dealing
+// of k_verify_service, which tests/test_gpu_svc_deal.py must fail on.  Every mutant only masks
+// wrongly, or skips a store it owes to a bitmap: none moves a load or a store, and none changes
+// what a wave counts as verified or what a block reports as complete, so every ticket still
+// completes and the grid still leaves on its stop.
+//   1  the flush of 64 stashed verdict words leaves out lane 63's store
+//   2  the rec < n mask takes n from the next mapped batch (nx.n), not the tile's own
+//   3  KEYSEL_ZERO with slot 0 empty: a wave's first tile is not failed closed, its word is the
+//      rec < n mask alone
+//   4  the flush in front of a wait for the host (c == kSvcPending) leaves out the last stashed
+//      word (reached where a wave runs out of published descriptors: live submits, or a relayed
+//      descriptor, the stop included, that the relay has not published yet)
+#ifndef HFV_MUT_SVCDEAL
+#define HFV_MUT_SVCDEAL 0
+#endif
 template <int KEYSEL>
 __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
 {
@@ -513,6 +528,11 @@ __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
     uint32_t fl_b = 0, fl_count = 0, fl_k = 0;   // ... and the count they complete (fl_k = 0: none)
     uint32_t dc_b = 0, dc_count = 0, dc_k = 0;   // stored last iteration: count after this wait
     uint32_t pending = 0;            // verified tiles of cur.b not handed to a count yet
+#if HFV_MUT_SVCDEAL == 3
+    bool first_tile = true;
+#elif HFV_MUT_SVCDEAL == 4
+    bool before_host_wait = false;
+#endif
     auto count = [&](uint32_t b, uint32_t cnt, uint32_t k) {   // stores acknowledged (caller waited)
         if (k && lane == 0) {
             const uint32_t old =
@@ -521,7 +541,13 @@ __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
         }
     };
     auto store_stash = [&]() {
+#if HFV_MUT_SVCDEAL == 1
+        if (lane < stashed && !(stashed == 64 && lane == 63))
+#elif HFV_MUT_SVCDEAL == 4
+        if (lane < stashed - (before_host_wait ? 1u : 0u))
+#else
         if (lane < stashed)
+#endif
             __hip_atomic_store(reinterpret_cast<GlobalU64 *>(st_bits) + st_tile, st_word, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_SYSTEM);
         stashed = 0;
@@ -548,7 +574,16 @@ __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
         if (c != kSvcFound) nx = cur;
         RecWords rn = load_tile<false>(nx, nx.tile, lane, inf_off, hf_off);
         uint64_t ballot = 0;   // KEYSEL_ZERO with slot 0 empty: every packet fails closed
-        if (keyok) ballot = verify_tile<KEYSEL>(rc, cur.tile * 64 + lane < cur.n, l, ukp);
+#if HFV_MUT_SVCDEAL == 2
+        const uint64_t n_own = nx.n;
+#else
+        const uint64_t n_own = cur.n;
+#endif
+        if (keyok) ballot = verify_tile<KEYSEL>(rc, cur.tile * 64 + lane < n_own, l, ukp);
+#if HFV_MUT_SVCDEAL == 3
+        if (!keyok && first_tile) ballot = __ballot(cur.tile * 64 + lane < n_own);
+        first_tile = false;
+#endif
         if (lane == stashed) {
             st_word = ballot;
             st_tile = cur.tile;
@@ -571,7 +606,13 @@ __global__ __launch_bounds__(kBlock) void k_verify_service(const SvcArgs args)
             count(dc_b, dc_count, dc_k);
             dc_k = 0;
             if (flush) {
+#if HFV_MUT_SVCDEAL == 4
+                before_host_wait = c == kSvcPending;
+#endif
                 store_stash();
+#if HFV_MUT_SVCDEAL == 4
+                before_host_wait = false;
+#endif
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 count(fl_b, fl_count, fl_k);
                 flush = false;

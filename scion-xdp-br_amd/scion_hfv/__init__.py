@@ -22,7 +22,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv.so")
 # the test build: the same library plus the test hooks (hfv_debug_relay_delay, _publish_delay,
-# _br_grid, _br_split, _batch_grid, _loop_host_stage); loaded only by tests (HFV_LIB), never by the product path
+# _br_grid, _br_split, _batch_grid, _loop_host_stage, _service_set_weights); loaded only by tests (HFV_LIB),
+# never by the product path
 TEST_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv_test.so")
 
 KEYSEL_ZERO = 0
@@ -751,6 +752,35 @@ class Ctx:
         if L.hfv_debug_service_weights(self._h, w) != 0:
             return None
         return [int(x) for x in w]
+
+    def service_weights_used(self):
+        """Diagnostic: the block weights the running / last service grid was launched with, in
+        service_weights' order (hfv_debug_service_weights_used)."""
+        w = (ctypes.c_uint32 * 9)()
+        L = lib()
+        L.hfv_debug_service_weights_used.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        if L.hfv_debug_service_weights_used(self._h, w) != 0:
+            return None
+        return [int(x) for x in w]
+
+    def service_grid(self):
+        """Diagnostic: the blocks of the last service grid (hfv_debug_service_blocks), or None."""
+        out = (ctypes.c_uint64 * 2048)()
+        g = ctypes.c_int(0)
+        L = lib()
+        L.hfv_debug_service_blocks.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                               ctypes.POINTER(ctypes.c_int)]
+        if L.hfv_debug_service_blocks(self._h, out, len(out), ctypes.byref(g)) != 0:
+            return None
+        return g.value
+
+    def debug_service_set_weights(self, w):
+        """Test-only: the block weights of the next service grid (per XCD 0..7, then block 0's),
+        each in [512, 2048]."""
+        arr = (ctypes.c_uint32 * 9)(*[int(x) for x in w])
+        L = lib()
+        L.hfv_debug_service_set_weights.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+        _check(L.hfv_debug_service_set_weights(self._h, arr))
 
     def service_timeline(self, nbatches):
         """Diagnostic: per batch of the last grid, (relay published, block 0 loaded) in us

@@ -17,7 +17,7 @@ set, and an empty batch's word is untouched.
 A mutant build (make tiledeal) already has the hook: run it with
 HFV_LIB=lib/libscionhfv_tiledealN.so HFV_TEST_BUILD_CHILD=1, which runs every test body in place.
 
-Out of scope: the resident service's own dealing (k_verify_service; tests/test_gpu_service.py),
+Out of scope: the resident service's own dealing (k_verify_service; tests/test_gpu_svc_deal.py),
 and the split of a launch at 2^31 tiles, which no test size reaches."""
 import numpy as np
 import pytest
