@@ -243,6 +243,30 @@ int hfv_extract_records_rx_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slo
 int hfv_verify_frames_rx(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
                          const uint32_t *ingress_ifindex, size_t n, void *recs, size_t stride, uint8_t *status,
                          uint64_t *pass_bits, void *stream);
+/* Frames in, verdict bits out, in ONE launch on `stream`: the parse and the hop-field MAC in one
+ * kernel, with no record in between.  No record buffer exists and the ctx's record layout plays no
+ * part; status is optional (NULL: not written).  For every input that hfv_verify_frames_rx accepts,
+ * pass_bits[0 .. (n+63)/64) is bit-identical to what that call writes (bits >= n of the last word
+ * are 0) and status[0..n) likewise, for the same frames, slot, len, ingress_ifindex, n, key table,
+ * keysel and internal-ifindex set.  Direction as above: ingress_ifindex NULL or an empty set means
+ * every frame is external; otherwise a frame is internal iff its ifindex is in the ctx's set and is
+ * judged with the SegID as it stands (path_processing.h:140-142), every other frame by the
+ * AS-ingress rule (path_processing.h:73-77).  The limits are those of "What these calls do NOT do"
+ * above.  Fail closed: KEYSEL_ZERO with slot 0 empty clears every bit (status is still written);
+ * KEYSEL_IFID clears the bit of a frame whose key slot is empty.
+ * Every bitmap word is written whole by one plain store, nothing is read-modify-written: the bitmap
+ * needs no initialisation.  frames is never written; nothing at or past frames + n*slot, len + n or
+ * ingress_ifindex + n is read; no bitmap word at or past (n+63)/64 and no status byte at or past n
+ * is touched.  No allocation, no host synchronisation; like every data-path call it first stops a
+ * running verify service.  Checks: frames, slot, len and n as hfv_extract_records; pass_bits
+ * non-NULL and 8-byte aligned; n == 0 returns 0 and touches nothing, even with NULL buffers. */
+int hfv_verify_frames_fused(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                            const uint32_t *ingress_ifindex, size_t n, uint8_t *status, uint64_t *pass_bits,
+                            void *stream);
+/* Same, then waits and stores the kernel's execution time (dispatch start/stop) in *kernel_ms. */
+int hfv_verify_frames_fused_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                                  const uint32_t *ingress_ifindex, size_t n, uint8_t *status, uint64_t *pass_bits,
+                                  void *stream, float *kernel_ms);
 /* One frame on the host: hfv_frame_locate, the copy of the two fields and, for from_internal != 0,
  * the normalisation above.  Returns the status; inf and hf are all zeros for a non-zero status;
  * -EINVAL for NULL arguments.  The scalar counterpart of hfv_extract_records_rx. */

@@ -347,6 +347,12 @@ struct LdsKey {              // per-lane slot from the LDS copy of the table
 constexpr int kSchedRows = 5;
 static __shared__ uint4 s_keys5[kSchedRows * HFV_MAX_KEYS];
 
+// TAB = 4 (the record verify kernels): rk2 plain, for round_full<4>.  TAB = 3 (k_verify_frames):
+// round_full<3> takes its round key rotated by 16, as the image stores rows 1..9, so rk2 stays as
+// stored and the schedule words are rotated instead: every step of next_round_key is a word-wise
+// XOR, which commutes with the rotation, so rk3..rk10 come out rotated too (cmac48_sched<3>
+// turns rk10 back for the final round).
+template <int TAB = 4>
 __device__ __forceinline__ void fill_keys5(const DevKeyTable *tab, uint32_t nthr)
 {
     // image rows 0 and 11 as stored; rk2 (image row 2, stored rotated by 16) unrotated; the
@@ -355,7 +361,7 @@ __device__ __forceinline__ void fill_keys5(const DevKeyTable *tab, uint32_t nthr
         const uint32_t j = e / HFV_MAX_KEYS, k = e % HFV_MAX_KEYS;
         const uint32_t *p = j < 3 ? tab->rows[j == 0 ? 0 : j == 1 ? 11 : 2][k] : tab->sched[j - 3][k];
         uint4 v = make_uint4(p[0], p[1], p[2], p[3]);
-        if (j == 2) v = make_uint4(rot16(v.x), rot16(v.y), rot16(v.z), rot16(v.w));
+        if (TAB == 4 ? j == 2 : j > 2) v = make_uint4(rot16(v.x), rot16(v.y), rot16(v.z), rot16(v.w));
         s_keys5[e] = v;
     }
     if (threadIdx.x < 8) s_valid[threadIdx.x] = tab->valid[threadIdx.x];
@@ -374,7 +380,8 @@ __device__ __forceinline__ uint4 next_round_key(const uint4 &rk, uint32_t t)
 
 __device__ __forceinline__ bool slot_valid(uint32_t slot) { return (s_valid[slot >> 5] >> (slot & 31)) & 1u; }
 
-// Tag words 0..1 of a record-derived macinput for the slot's key (s_keys5).
+// Tag words 0..1 of a record-derived macinput for the slot's key (s_keys5 as fill_keys5<TAB> left it).
+template <int TAB = 4>
 __device__ __forceinline__ void cmac48_sched(const uint32_t w[4], uint32_t slot, const Lane &l, uint32_t &t0,
                                              uint32_t &t1)
 {
@@ -384,15 +391,19 @@ __device__ __forceinline__ void cmac48_sched(const uint32_t w[4], uint32_t slot,
     const uint4 ta = s_keys5[3 * HFV_MAX_KEYS + slot], tb = s_keys5[4 * HFV_MAX_KEYS + slot];
     const uint32_t t[8] = {ta.x, ta.y, ta.z, ta.w, tb.x, tb.y, tb.z, tb.w};
     uint32_t s[4] = {w[0] ^ k0.x, w[1] ^ k0.y, w[2] ^ k0.z, w[3] ^ k0.w};
-    round1_macinput<4>(s, r1, l);
-    round_full<4>(s, rk, l);
+    round1_macinput<TAB>(s, r1, l);
+    round_full<TAB>(s, rk, l);
 #pragma unroll
     for (int r = 3; r < 10; ++r) {
         rk = next_round_key(rk, t[r - 3]);
-        round_full<4>(s, rk, l);
+        round_full<TAB>(s, rk, l);
     }
     rk = next_round_key(rk, t[7]);                 // rk10
-    round_last_48<4>(s, rk, l, t0, t1);
+    if constexpr (TAB != 4) {                      // ... rotated like rk2..rk9; the final round takes x and y plain
+        rk.x = rot16(rk.x);
+        rk.y = rot16(rk.y);
+    }
+    round_last_48<TAB>(s, rk, l, t0, t1);
 }
 
 // Tag words 0..1 for a record-derived macinput w[] (bytes 0,1,8,14,15 zero).

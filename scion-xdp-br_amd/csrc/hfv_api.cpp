@@ -57,7 +57,8 @@ LaunchGeom br_geom(const hfv_ctx *ctx)
 // hfv_debug_batch_grid: blocks per k_verify_batches launch (0 = one block per CU up to the tile
 // count), for every call that ends in launch_verify_batches.  With 1 to 3 blocks a list of a few
 // thousand tiles gives every wave a hundred tiles and more over many batches -- the dealing the real
-// grid reaches only at 2^24 records (tests/test_gpu_tile_deal.py).
+// grid reaches only at 2^24 records (tests/test_gpu_tile_deal.py).  The same cap holds for the
+// k_verify_frames launch of hfv_verify_frames_fused (tests/test_gpu_frames_fused.py).
 static unsigned g_batch_grid = 0;
 extern "C" int hfv_debug_batch_grid(unsigned blocks)
 {
@@ -446,16 +447,25 @@ int hfv_verify_batches_timed(hfv_ctx *ctx, const struct hfv_batch *batches, size
 
 // ---- frames -> records -> verdict bits ---------------------------------------------------
 
+// What every frame call checks of the frames themselves.
+static int frame_args_check(const uint8_t *frames, size_t slot, const uint16_t *len, size_t n)
+{
+    if (!frames || !len) return fail(-EINVAL, "null buffer");
+    if ((slot & 7) || slot < 64) return fail(-EINVAL, "slot %zu: must be a multiple of 8, at least 64", slot);
+    if (slot > (1u << 24)) return fail(-EINVAL, "slot %zu > 16 MiB", slot);
+    if (n > ((size_t)1 << 36)) return fail(-EINVAL, "%zu frames (at most 2^36)", n);
+    return 0;
+}
+
 static int frames_check(const hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len, size_t n,
                         const void *recs, size_t stride, const uint8_t *status)
 {
-    if (!frames || !len || !status) return fail(-EINVAL, "null buffer");
-    if ((slot & 7) || slot < 64) return fail(-EINVAL, "slot %zu: must be a multiple of 8, at least 64", slot);
-    if (slot > (1u << 24)) return fail(-EINVAL, "slot %zu > 16 MiB", slot);
-    int rc = check_records(ctx, recs, stride, recs);   // no bitmap here: hfv_verify_frames_rx checks its own
+    if (!status) return fail(-EINVAL, "null buffer");
+    int rc = frame_args_check(frames, slot, len, n);
+    if (rc) return rc;
+    rc = check_records(ctx, recs, stride, recs);   // no bitmap here: hfv_verify_frames_rx checks its own
     if (rc) return rc;
     if (stride > (1u << 24)) return fail(-EINVAL, "stride %zu > 16 MiB", stride);
-    if (n > ((size_t)1 << 36)) return fail(-EINVAL, "%zu frames (at most 2^36)", n);
     return 0;
 }
 
@@ -549,6 +559,59 @@ int hfv_verify_frames(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const ui
     return hfv_verify_frames_rx(ctx, frames, slot, len, nullptr, n, recs, stride, status, pass_bits, stream);
 }
 
+// Frames in, verdict bits out, in one launch (k_verify_frames): no records, no scratch, the ctx's
+// record layout plays no part.  frame_args_check bounds n at 2^36 frames = 2^30 tiles, below the
+// 2^31 tiles one launch may take, so the call is always one launch.  Under KEYSEL_ZERO the kernel
+// takes slot 0 from its arguments and reads no device table (launch_reads_tables).  ctx is not
+// NULL and n != 0.
+static int verify_frames_fused(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                               const uint32_t *ingress_ifindex, size_t n, uint8_t *status, uint64_t *pass_bits,
+                               void *stream, hipEvent_t ev0, hipEvent_t ev1)
+{
+    int rc = frame_args_check(frames, slot, len, n);
+    if (rc) return rc;
+    if (!pass_bits) return fail(-EINVAL, "null buffer");
+    if ((uintptr_t)pass_bits & 7) return fail(-EINVAL, "bitmap must be 8-byte aligned");
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    const bool reader = launch_reads_tables(ctx->keysel);
+    return with_tables(ctx, (hipStream_t)stream, "verify_frames_fused launch", reader, [&](DevState *ds) {
+        FusedArgs a;
+        memset(&a, 0, sizeof a);
+        a.frames = frames;
+        a.slot = slot;
+        a.lens = len;
+        a.ifindex = ingress_ifindex;
+        a.n = n;
+        a.status = status;
+        a.bits = (unsigned long long *)pass_bits;
+        a.tab = &ds->keys;
+        a.set = ctx->rx_set;
+        return launch_verify_frames(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, stream, ev0, ev1);
+    });
+}
+
+int hfv_verify_frames_fused(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                            const uint32_t *ingress_ifindex, size_t n, uint8_t *status, uint64_t *pass_bits,
+                            void *stream)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    return verify_frames_fused(ctx, frames, slot, len, ingress_ifindex, n, status, pass_bits, stream, nullptr, nullptr);
+}
+
+int hfv_verify_frames_fused_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                                  const uint32_t *ingress_ifindex, size_t n, uint8_t *status, uint64_t *pass_bits,
+                                  void *stream, float *kernel_ms)
+{
+    if (!ctx || !kernel_ms) return fail(-EINVAL, "null argument");
+    *kernel_ms = 0.0f;
+    if (n == 0) return 0;
+    return timed(ctx, kernel_ms, [&](hipEvent_t ev0, hipEvent_t ev1) {
+        return verify_frames_fused(ctx, frames, slot, len, ingress_ifindex, n, status, pass_bits, stream, ev0, ev1);
+    });
+}
+
 // Diagnostic (not part of include/scion_hfv.h): the last step of hfv_verify_frames alone,
 // pass_bits[i / 64] &= (status[i] == 0), so that scripts/frames_probe.py can time the mask kernel.
 extern "C" int hfv_debug_mask_status(hfv_ctx *ctx, const uint8_t *status, size_t n, uint64_t *pass_bits, void *stream)
@@ -618,7 +681,10 @@ int hfv_ctx_describe(const hfv_ctx *ctx, char *buf, size_t len)
     snprintf(buf, len,
              "verify: 1024-thread blocks, one per CU (%d CUs), four 32x-replicated round tables in LDS (128 KiB), "
              "T0 and slot-0 key rows in the kernel arguments; keysel ifid: five 16 B LDS rows per slot "
-             "(round-1 folded key, rk2, schedule words of rounds 3..10); service grid %d blocks",
+             "(round-1 folded key, rk2, schedule words of rounds 3..10); service grid %d blocks; "
+             "verify_frames_fused: one block per CU, two 8x-replicated round tables (16 KiB) beside 132 B staged "
+             "rows per frame, 1024-thread blocks (keysel zero, 151556 B LDS) or 768-thread blocks with the "
+             "per-slot key rows (keysel ifid, 138276 B LDS)",
              ctx->geom.num_cus, ctx->geom.svc_blocks);
     return 0;
 }

@@ -333,6 +333,28 @@ int launch_extract_records_rx(const uint8_t *frames, size_t slot, const uint16_t
 // pass_bits[i / 64] &= ballot(status[i] == 0), the last step of hfv_verify_frames
 int launch_mask_status(const uint8_t *status, size_t n, uint64_t *bits, void *stream);
 
+// frames -> verdict bits in one launch (hfv_frames_fused_kernel.hip, hfv_verify_frames_fused): the
+// one by-value kernel argument.  The caller fills everything above key0; the launcher fills the
+// slot-0 key rows from the key table as last published (key_prologue).  ifindex null or an empty
+// set: every frame is external.  tab is read under KEYSEL_IFID only.
+struct FusedArgs {
+    const uint8_t *frames;
+    uint64_t slot;
+    const uint16_t *lens;
+    const uint32_t *ifindex;
+    uint64_t n;
+    uint8_t *status;               // nullable
+    unsigned long long *bits;
+    const DevKeyTable *tab;
+    RxSet set;
+    uint32_t key0[kDevKeyRows * 4];
+    uint32_t key0_ok;
+};
+// One persistent grid of one block per CU (16 waves under KEYSEL_ZERO, 12 under KEYSEL_IFID), capped
+// by g.batch_grid_cap in the test build; the staged kernel where launch_extract_records would stage.
+int launch_verify_frames(const LaunchGeom &g, int keysel, FusedArgs a, const DevKeyTable *host_keys, void *stream,
+                         void *ev_start = nullptr, void *ev_stop = nullptr);
+
 // pinned key map (hfv_keymap.cpp)
 int keymap_open_ro(const char *path, const void **mapping);
 int keymap_create(const char *path, uint32_t mode);   // empty map (header only) if the file does not exist

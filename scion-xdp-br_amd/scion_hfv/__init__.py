@@ -90,6 +90,8 @@ def lib():
         "hfv_extract_records_rx_timed": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp,
                                                ctypes.POINTER(ctypes.c_float)]),
         "hfv_verify_frames_rx": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]),
+        "hfv_verify_frames_fused": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp]),
+        "hfv_verify_frames_fused_timed": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]),
         "hfv_frame_extract": (i32, [vp, sz, i32, vp, vp]),
         "hfv_ctx_describe": (i32, [vp, ctypes.c_char_p, sz]),
         "hfv_ctx_attach_keymap": (i32, [vp, ctypes.c_char_p]),
@@ -547,6 +549,21 @@ class Ctx:
         _check(lib().hfv_verify_frames_rx(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
                                           _ptr(recs), stride, _ptr(status), _ptr(pass_bits), _stream(stream)))
 
+    def verify_frames_fused(self, frames, slot, lens, n, pass_bits, ingress_ifindex=None, status=None, stream=None):
+        """hfv_verify_frames_fused: frames in, verdict bits out, in one launch -- no record buffer, the
+        status bytes optional.  The bits (and status) are those of verify_frames_rx; every bitmap
+        word is stored whole, so pass_bits needs no initialisation."""
+        _check(lib().hfv_verify_frames_fused(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
+                                             _ptr(status), _ptr(pass_bits), _stream(stream)))
+
+    def verify_frames_fused_timed(self, frames, slot, lens, n, pass_bits, ingress_ifindex=None, status=None,
+                                  stream=None):
+        """verify_frames_fused, waited for; returns the kernel's execution time in ms."""
+        ms = ctypes.c_float(0.0)
+        _check(lib().hfv_verify_frames_fused_timed(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
+                                                   _ptr(status), _ptr(pass_bits), _stream(stream), ctypes.byref(ms)))
+        return ms.value
+
     def mask_status(self, status, n, pass_bits, stream=None):
         """Diagnostic (hfv_debug_mask_status): verify_frames' last step alone,
         pass_bits[i / 64] &= (status[i] == 0)."""
@@ -618,7 +635,7 @@ class Ctx:
     @staticmethod
     def debug_batch_grid(blocks):
         """Test-only: cap k_verify_batches launches (verify_batches, verify_records, verify_frames)
-        at `blocks` blocks (0 = default geometry)."""
+        and k_verify_frames launches (verify_frames_fused) at `blocks` blocks (0 = default geometry)."""
         _check(lib().hfv_debug_batch_grid(ctypes.c_uint(blocks)))
 
     @staticmethod

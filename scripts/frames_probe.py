@@ -25,6 +25,15 @@ in the same run, over the frames decided by the MAC (the router's verdict is SCI
 INVALID_HF, and a frame from the internal link has an AS-egress IFID with a fwd_external egress
 entry).  Every other field is what a run without --rx reports; the default --out becomes
 profiles/frames/frames_rx_probe.json.
+
+--fused adds, per slot under "fused", hfv_verify_frames_fused (frames to verdict bits in one launch)
+with the mix's ifindex array and BR 1's internal ifindices, against the three-launch
+hfv_verify_frames_rx on the same frames in the same run: the fused kernel's dispatch time
+(hfv_verify_frames_fused_timed), then, interleaved rep by rep, the stream-event region around the
+plain fused call, the region around hfv_verify_frames_rx, and hfv_br_process_timed (the router over
+a copy of the frames runs ahead of either region, so both find the frame buffer in the same state),
+and each region back to back with itself; medians and the whole range of each, whether the fused
+range lies below the three-launch range, and whether the two bitmaps are equal.  The default --out becomes profiles/frames/frames_fused_probe.json.
 """
 import argparse
 import json
@@ -126,6 +135,57 @@ def rx_leg(torch, hfv, ctx, cfg, internal_ifx, frames, tid, ifx, master, slot, d
     return r
 
 
+def fused_leg(torch, ctx, internal_ifx, master, slot, d_len, d_if, n, recs, status, bits, act, ver, egr, warmup, reps):
+    """The one-launch path against the three-launch path and the router, interleaved."""
+    ctx.set_internal_ifindices(internal_ifx)
+    fbits = torch.empty_like(bits)
+    work = torch.empty_like(master)
+    fused = lambda: ctx.verify_frames_fused(master, slot, d_len, n, fbits, ingress_ifindex=d_if)   # noqa: E731
+    three = lambda: ctx.verify_frames_rx(master, slot, d_len, d_if, n, recs, status, bits)   # noqa: E731
+
+    def router():
+        work.copy_(master)
+        return ctx.br_process_timed(work, slot, d_len, d_if, n, act, ver, egr)
+
+    for _ in range(warmup):
+        ctx.verify_frames_fused_timed(master, slot, d_len, n, fbits, ingress_ifindex=d_if)
+        fused()
+        three()
+        router()
+    torch.cuda.synchronize()
+    disp = [ctx.verify_frames_fused_timed(master, slot, d_len, n, fbits, ingress_ifindex=d_if) for _ in range(reps)]
+    # interleaved, every timed region behind the same predecessor (the router over a copy of the frames:
+    # 2 x frame_bytes of other traffic), so neither path finds the frames left warm by the other
+    f, t, b = [], [], []
+    for _ in range(reps):
+        b.append(router())
+        f += region_ms(torch, fused, 1)
+        router()
+        t += region_ms(torch, three, 1)
+    # and each path back to back with itself, as verify_frames_region_ms above is taken
+    fw, tw = region_ms(torch, fused, reps), region_ms(torch, three, reps)
+    r = {"internal_ifindices": internal_ifx}
+    for name, xs in (("fused_dispatch_ms", disp), ("fused_region_ms", f), ("three_launch_region_ms", t),
+                     ("fused_region_back_to_back_ms", fw), ("three_launch_region_back_to_back_ms", tw),
+                     ("br_process_ms", b)):
+        r[name] = round(med(xs), 5)
+        r[name + "_min_max"] = [round(min(xs), 5), round(max(xs), 5)]
+    r["fused_over_three_launch"] = round(med(f) / med(t), 4)
+    r["fused_over_router"] = round(med(f) / med(b), 4)
+    r["fused_range_below_three_launch_range"] = bool(max(f) < min(t))
+    r["fused_range_below_three_launch_range_back_to_back"] = bool(max(fw) < min(tw))
+    fused()
+    three()
+    torch.cuda.synchronize()
+    r["bitmaps_equal"] = bool(torch.equal(fbits, bits))
+    r["frames_passed"] = int(np.unpackbits(fbits.cpu().numpy().view(np.uint8)).sum())
+    # and with no status buffer against one given: the same launch, n more bytes stored
+    st = [ctx.verify_frames_fused_timed(master, slot, d_len, n, fbits, ingress_ifindex=d_if, status=status)
+          for _ in range(reps)]
+    r["fused_dispatch_with_status_ms"] = round(med(st), 5)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -135,10 +195,12 @@ def main():
     ap.add_argument("--direct", action="store_true", help="misalign the frame buffer: the direct kernel")
     ap.add_argument("--extract-only", action="store_true", help="A/B runs: the extract kernel alone")
     ap.add_argument("--rx", action="store_true", help="add the direction-aware path (see above)")
+    ap.add_argument("--fused", action="store_true", help="add the one-launch path (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "frames", "frames_rx_probe.json" if args.rx else "frames_probe.json")
+        name = "frames_fused_probe.json" if args.fused else "frames_rx_probe.json" if args.rx else "frames_probe.json"
+        args.out = os.path.join(ROOT, "profiles", "frames", name)
     args.extract_only |= args.direct   # the other legs want the aligned buffer
     import torch
     import bench
@@ -251,6 +313,9 @@ def main():
         if args.rx:
             r["rx"] = rx_leg(torch, hfv, ctx, cfg, internal_ifx, frames, tid, ifx, master, slot, d_len, d_if, n, recs,
                              status, bits, None if args.extract_only else ver, args.warmup, reps)
+        if args.fused:
+            r["fused"] = fused_leg(torch, ctx, internal_ifx, master, slot, d_len, d_if, n, recs, status, bits, act, ver,
+                                   egr, args.warmup, reps)
         result["slots"][str(slot)] = r
         del master, buf
     ctx.close()

@@ -21,7 +21,7 @@ def main(d, sizes, kernel="k_verify_records", per=1):
             e["name"] = r["Kernel_Name"]
             e["c"][r["Counter_Name"]] += float(r["Counter_Value"])
         group, first = -1, False
-        if not kernel.startswith("k_verify"):   # one batch size: every launch of `kernel` but the first
+        if not kernel.startswith("k_verify") or kernel == "k_verify_frames":   # one batch size: every launch of `kernel` but the first
             group, first = 0, True
         prev_gen = False
         for did in sorted(disp):
