@@ -267,6 +267,49 @@ int hfv_verify_frames_fused(hfv_ctx *ctx, const uint8_t *frames, size_t slot, co
 int hfv_verify_frames_fused_timed(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
                                   const uint32_t *ingress_ifindex, size_t n, uint8_t *status, uint64_t *pass_bits,
                                   void *stream, float *kernel_ms);
+/* One batch of the frame list of hfv_verify_frames_batches: the arguments hfv_verify_frames_fused
+ * takes for one batch. */
+struct hfv_frame_batch {            /* 56 bytes */
+    const uint8_t *frames;          /* frame i at frames + i*slot */
+    size_t slot;
+    const uint16_t *len;
+    const uint32_t *ingress_ifindex;/* nullable: every frame of this batch is external */
+    size_t n;
+    uint8_t *status;                /* nullable: not written */
+    uint64_t *pass_bits;            /* (n+63)/64 words, 8-byte aligned */
+};
+/* hfv_verify_frames_fused over `count` batches in as few launches as the list allows: what
+ * hfv_verify_batches is to hfv_verify_records.  The round tables are written into LDS once per
+ * launch and the batches' tiles are dealt to the CUs as one contiguous range, so a list of ring
+ * chunks pays the table fill, the grid's ramp and tail and the launch once, not once per chunk.
+ * One launch holds up to 32 consecutive non-empty batches (and 2^31 tiles) that are all staged
+ * (slot >= 128, slot % 16 == 0, frames 16-byte aligned) or all not; a longer or mixed list is split,
+ * in list order.
+ * For every batch j with n != 0, pass_bits and status hold bit for bit what
+ * hfv_verify_frames_fused(ctx, frames, slot, len, ingress_ifindex, n, status, pass_bits, stream)
+ * writes for that batch, under the ctx's key table, keysel and internal-ifindex set at the time of
+ * the call: bits at or past n of a batch's last word are 0; every bitmap word is written whole by
+ * one plain store, so no initialisation is needed; no bitmap word at or past (n+63)/64 and no
+ * status byte at or past n is touched; nothing at or past frames + n*slot, len + n or
+ * ingress_ifindex + n is read; no input is written.
+ * Stream-ordered: the call reads what earlier work on `stream` wrote and its outputs are complete
+ * for later work on it; it allocates nothing and does not synchronise the host.  Like every
+ * data-path call it first stops a running verify service.  Key-table publication holds as for
+ * hfv_verify_frames_fused: a launch keeps the table it was launched with.
+ * Empty batches (n == 0) are skipped and their pointers are not looked at; count == 0, or a list of
+ * empty batches only, returns 0 and launches nothing (the tables are still published).
+ * All batches are checked before anything is launched: frames, slot, len and n as
+ * hfv_extract_records; pass_bits non-NULL and 8-byte aligned.  A bad batch k returns -EINVAL with
+ * "batch k: ..." in hfv_last_error(), and no output of any batch has been touched.  NULL ctx, or
+ * NULL batches with count > 0: -EINVAL.
+ * Outputs of different batches must not overlap.  Inputs may be shared: the same frames may appear
+ * in two batches with different ifindex arrays. */
+int hfv_verify_frames_batches(hfv_ctx *ctx, const struct hfv_frame_batch *batches, size_t count, void *stream);
+/* Same, then waits and stores the launches' execution time (dispatch start of the first to
+ * dispatch end of the last) in *kernel_ms; 0.0 and 0 when nothing is launched.  NULL kernel_ms:
+ * -EINVAL. */
+int hfv_verify_frames_batches_timed(hfv_ctx *ctx, const struct hfv_frame_batch *batches, size_t count,
+                                    void *stream, float *kernel_ms);
 /* One frame on the host: hfv_frame_locate, the copy of the two fields and, for from_internal != 0,
  * the normalisation above.  Returns the status; inf and hf are all zeros for a non-zero status;
  * -EINVAL for NULL arguments.  The scalar counterpart of hfv_extract_records_rx. */

@@ -58,7 +58,8 @@ LaunchGeom br_geom(const hfv_ctx *ctx)
 // count), for every call that ends in launch_verify_batches.  With 1 to 3 blocks a list of a few
 // thousand tiles gives every wave a hundred tiles and more over many batches -- the dealing the real
 // grid reaches only at 2^24 records (tests/test_gpu_tile_deal.py).  The same cap holds for the
-// k_verify_frames launch of hfv_verify_frames_fused (tests/test_gpu_frames_fused.py).
+// k_verify_frames launch of hfv_verify_frames_fused (tests/test_gpu_frames_fused.py) and the
+// k_verify_frames_list launches of hfv_verify_frames_batches (tests/test_gpu_frames_list.py).
 static unsigned g_batch_grid = 0;
 extern "C" int hfv_debug_batch_grid(unsigned blocks)
 {
@@ -609,6 +610,95 @@ int hfv_verify_frames_fused_timed(hfv_ctx *ctx, const uint8_t *frames, size_t sl
     if (n == 0) return 0;
     return timed(ctx, kernel_ms, [&](hipEvent_t ev0, hipEvent_t ev1) {
         return verify_frames_fused(ctx, frames, slot, len, ingress_ifindex, n, status, pass_bits, stream, ev0, ev1);
+    });
+}
+
+// The batch list of hfv_verify_frames_batches: every non-empty batch checked as
+// hfv_verify_frames_fused checks one, before anything is launched.
+static int frames_batches_check(const struct hfv_frame_batch *b, size_t count)
+{
+    if (!b && count) return fail(-EINVAL, "null batch list");
+    for (size_t i = 0; i < count; ++i) {
+        if (b[i].n == 0) continue;
+        int rc = frame_args_check(b[i].frames, b[i].slot, b[i].len, b[i].n);
+        if (rc) return fail_batch(rc, i);
+        if (!b[i].pass_bits) return fail(-EINVAL, "batch %zu: null buffer", i);
+        if ((uintptr_t)b[i].pass_bits & 7) return fail(-EINVAL, "batch %zu: bitmap must be 8-byte aligned", i);
+    }
+    return 0;
+}
+
+// One k_verify_frames_list launch per run of consecutive non-empty batches that are all staged or
+// all direct (the rule of launch_verify_frames), of at most kFrameBatchMax batches and 2^31 tiles,
+// in list order; ev0/ev1 (nullable) bracket the first and the last launch.
+static int frames_batches_launch(hfv_ctx *ctx, const struct hfv_frame_batch *b, size_t count, hipStream_t st,
+                                 hipEvent_t ev0, hipEvent_t ev1)
+{
+    size_t last = count;   // the last non-empty batch: its launch records ev1
+    while (last > 0 && b[last - 1].n == 0) --last;
+    const bool reader = launch_reads_tables(ctx->keysel);
+    return with_tables(ctx, st, "verify_frames_batches launch", reader, [&](DevState *ds) {
+        if (last == 0) return (int)hipSuccess;   // nothing to launch: the tables are published all the same
+        FusedListArgs a;
+        memset(&a, 0, sizeof a);
+        a.tab = &ds->keys;
+        a.set = ctx->rx_set;
+        const KeyPrologue pro = key_prologue(&ctx->host_img->keys);
+        memcpy(a.key0, pro.key0, sizeof a.key0);
+        a.key0_ok = pro.key0_ok;
+        auto stageable = [](const struct hfv_frame_batch &x) { return frames_stageable(x.frames, x.slot); };
+        for (size_t i = 0;;) {
+            a.nb = 0;
+            uint64_t tiles = 0;
+            bool staged = false;
+            for (; i < last && a.nb < kFrameBatchMax; ++i) {
+                if (b[i].n == 0) continue;
+                const uint64_t t = (b[i].n + 63) / 64;
+                if (a.nb && (tiles + t > (1ull << 31) || stageable(b[i]) != staged)) break;
+                staged = stageable(b[i]);
+                // no set: every frame is external, and no ifindex is loaded
+                const uint32_t *ifx = a.set.n ? b[i].ingress_ifindex : nullptr;
+                a.d[a.nb] = {(uint64_t)(uintptr_t)b[i].frames, (uint64_t)(uintptr_t)b[i].len, (uint64_t)(uintptr_t)ifx,
+                             (uint64_t)(uintptr_t)b[i].status, (uint64_t)(uintptr_t)b[i].pass_bits, (uint64_t)b[i].n,
+                             (uint32_t)b[i].slot, 0u};
+                a.cum[a.nb] = (uint32_t)tiles;
+                tiles += t;
+                ++a.nb;
+            }
+            a.cum[a.nb] = (uint32_t)tiles;
+            a.total = (uint32_t)tiles;
+            const bool fin = i >= last;
+            int e = launch_verify_frames_list(batch_geom(ctx), ctx->keysel, staged, a, st, ev0, fin ? ev1 : nullptr);
+            if (e != hipSuccess || fin) return e;   // with_tables notes the last launch
+            if (reader) note_reader(ctx, st);
+            ev0 = nullptr;
+        }
+    });
+}
+
+int hfv_verify_frames_batches(hfv_ctx *ctx, const struct hfv_frame_batch *batches, size_t count, void *stream)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    int rc = frames_batches_check(batches, count);
+    if (rc) return rc;
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    return frames_batches_launch(ctx, batches, count, (hipStream_t)stream, nullptr, nullptr);
+}
+
+int hfv_verify_frames_batches_timed(hfv_ctx *ctx, const struct hfv_frame_batch *batches, size_t count, void *stream,
+                                    float *kernel_ms)
+{
+    if (!ctx || !kernel_ms) return fail(-EINVAL, "null argument");
+    *kernel_ms = 0.0f;
+    int rc = frames_batches_check(batches, count);
+    if (rc) return rc;
+    size_t nonempty = 0;
+    for (size_t i = 0; i < count; ++i) nonempty += batches[i].n != 0;
+    if (!nonempty) return 0;
+    return timed(ctx, kernel_ms, [&](hipEvent_t ev0, hipEvent_t ev1) {
+        SVC_QUIESCE(ctx);
+        return frames_batches_launch(ctx, batches, count, (hipStream_t)stream, ev0, ev1);
     });
 }
 

@@ -355,6 +355,38 @@ struct FusedArgs {
 int launch_verify_frames(const LaunchGeom &g, int keysel, FusedArgs a, const DevKeyTable *host_keys, void *stream,
                          void *ev_start = nullptr, void *ev_stop = nullptr);
 
+// A list of frame batches in one launch (hfv_verify_frames_batches, k_verify_frames_list): up to
+// kFrameBatchMax batches, their descriptors and the running tile count cum[] (batch j = global
+// tiles [cum[j], cum[j+1]), cum[nb] = total) in the one by-value kernel argument, beside what
+// FusedArgs carries for every batch alike.  64 of the 56-byte descriptors would not fit the 4 KiB
+// kernarg segment beside the key rows and the set; 32 do.  ifindex 0: every frame of the batch is
+// external (the host also stores 0 where the set is empty); status 0: not written.
+constexpr uint32_t kFrameBatchMax = 32;
+struct FrameDesc {
+    uint64_t frames, lens, ifindex, status, bits, n;   // device pointers / the frame count
+    uint32_t slot, pad_;
+};
+struct FusedListArgs {
+    const DevKeyTable *tab;   // read under KEYSEL_IFID only
+    RxSet set;
+    uint32_t key0[kDevKeyRows * 4];
+    uint32_t key0_ok;
+    uint32_t nb, total;       // batches; tiles over all of them (at most 2^31)
+    FrameDesc d[kFrameBatchMax];
+    uint32_t cum[kFrameBatchMax + 1];
+};
+static_assert(sizeof(FrameDesc) == 56 && offsetof(FusedListArgs, set) == 8 && offsetof(FusedListArgs, key0) == 76 &&
+                  offsetof(FusedListArgs, nb) == 272 && offsetof(FusedListArgs, d) == 280 &&
+                  offsetof(FusedListArgs, cum) == 2072 && sizeof(FusedListArgs) == 2208,
+              "FusedListArgs layout");
+static_assert(sizeof(FusedListArgs) <= 4096, "FusedListArgs exceeds the 4 KiB kernel-argument segment");
+// The staging rule of launch_verify_frames: slot >= 128, slot % 16 == 0, frames 16-byte aligned.
+bool frames_stageable(const uint8_t *frames, size_t slot);
+// The launch of one run of batches that are all stageable (staged) or all not; the grid as
+// launch_verify_frames, over a.total tiles.
+int launch_verify_frames_list(const LaunchGeom &g, int keysel, bool staged, const FusedListArgs &a, void *stream,
+                              void *ev_start = nullptr, void *ev_stop = nullptr);
+
 // pinned key map (hfv_keymap.cpp)
 int keymap_open_ro(const char *path, const void **mapping);
 int keymap_create(const char *path, uint32_t mode);   // empty map (header only) if the file does not exist

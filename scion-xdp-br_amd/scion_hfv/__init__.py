@@ -92,6 +92,8 @@ def lib():
         "hfv_verify_frames_rx": (i32, [vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, vp]),
         "hfv_verify_frames_fused": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp]),
         "hfv_verify_frames_fused_timed": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]),
+        "hfv_verify_frames_batches": (i32, [vp, vp, sz, vp]),
+        "hfv_verify_frames_batches_timed": (i32, [vp, vp, sz, vp, ctypes.POINTER(ctypes.c_float)]),
         "hfv_frame_extract": (i32, [vp, sz, i32, vp, vp]),
         "hfv_ctx_describe": (i32, [vp, ctypes.c_char_p, sz]),
         "hfv_ctx_attach_keymap": (i32, [vp, ctypes.c_char_p]),
@@ -268,6 +270,13 @@ def verify_macinput(macinput: bytes, expected: int, hop_key_bytes) -> bool:
 class HfvBatch(ctypes.Structure):
     """struct hfv_batch (hfv_service_submitv)"""
     _fields_ = [("recs", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("n", ctypes.c_size_t),
+                ("pass_bits", ctypes.c_void_p)]
+
+
+class FrameBatch(ctypes.Structure):
+    """struct hfv_frame_batch (hfv_verify_frames_batches); 56 bytes"""
+    _fields_ = [("frames", ctypes.c_void_p), ("slot", ctypes.c_size_t), ("len", ctypes.c_void_p),
+                ("ingress_ifindex", ctypes.c_void_p), ("n", ctypes.c_size_t), ("status", ctypes.c_void_p),
                 ("pass_bits", ctypes.c_void_p)]
 
 
@@ -564,6 +573,38 @@ class Ctx:
                                                    _ptr(status), _ptr(pass_bits), _stream(stream), ctypes.byref(ms)))
         return ms.value
 
+    @staticmethod
+    def frame_batches(batches):
+        """A struct hfv_frame_batch array from a sequence of FrameBatch or of
+        (frames, slot, lens, n, pass_bits[, ingress_ifindex[, status]]) tuples; an array made here
+        before is taken as it is (len(array) batches: make it of a non-empty list)."""
+        if isinstance(batches, ctypes.Array):
+            return batches
+        arr = (FrameBatch * max(len(batches), 1))()
+        for i, b in enumerate(batches):
+            if isinstance(b, FrameBatch):
+                arr[i] = b
+                continue
+            frames, slot, lens, n, pass_bits = b[:5]
+            ifx = b[5] if len(b) > 5 else None
+            status = b[6] if len(b) > 6 else None
+            arr[i] = FrameBatch(_ptr(frames), slot, _ptr(lens), _ptr(ifx), n, _ptr(status), _ptr(pass_bits))
+        return arr
+
+    def verify_frames_batches(self, batches, stream=None):
+        """hfv_verify_frames_batches: verify_frames_fused over every batch of the list in as few
+        launches as it allows (32 batches per launch, staged and direct batches apart).  Empty
+        batches are skipped."""
+        arr = self.frame_batches(batches)
+        _check(lib().hfv_verify_frames_batches(self._h, arr, len(batches), _stream(stream)))
+
+    def verify_frames_batches_timed(self, batches, stream=None):
+        """verify_frames_batches, waited for; returns the launches' execution time in ms."""
+        arr = self.frame_batches(batches)
+        ms = ctypes.c_float(0.0)
+        _check(lib().hfv_verify_frames_batches_timed(self._h, arr, len(batches), _stream(stream), ctypes.byref(ms)))
+        return ms.value
+
     def mask_status(self, status, n, pass_bits, stream=None):
         """Diagnostic (hfv_debug_mask_status): verify_frames' last step alone,
         pass_bits[i / 64] &= (status[i] == 0)."""
@@ -635,7 +676,8 @@ class Ctx:
     @staticmethod
     def debug_batch_grid(blocks):
         """Test-only: cap k_verify_batches launches (verify_batches, verify_records, verify_frames)
-        and k_verify_frames launches (verify_frames_fused) at `blocks` blocks (0 = default geometry)."""
+        and k_verify_frames / k_verify_frames_list launches (verify_frames_fused, verify_frames_batches)
+        at `blocks` blocks (0 = default geometry)."""
         _check(lib().hfv_debug_batch_grid(ctypes.c_uint(blocks)))
 
     @staticmethod

@@ -34,6 +34,15 @@ plain fused call, the region around hfv_verify_frames_rx, and hfv_br_process_tim
 a copy of the frames runs ahead of either region, so both find the frame buffer in the same state),
 and each region back to back with itself; medians and the whole range of each, whether the fused
 range lies below the three-launch range, and whether the two bitmaps are equal.  The default --out becomes profiles/frames/frames_fused_probe.json.
+
+--list adds, per slot under "list", hfv_verify_frames_batches over the frames cut into K chunks of c
+frames (c = 16384, K = 64 and c = 32768, K = 32 at the default --n) against K hfv_verify_frames_fused
+calls over the same chunks and against one fused call over all frames: interleaved rep by rep, the
+stream-event region around one list call, the region around the K calls, the list's dispatch time
+(hfv_verify_frames_batches_timed) and the one call's (hfv_verify_frames_fused_timed); medians and the
+whole range of each, whether the list region's range lies below the K-call region's, the list's
+dispatch median over the one call's, and whether the bitmaps of the two ways are equal.  The default
+--out becomes profiles/frames/frames_list_probe.json.
 """
 import argparse
 import json
@@ -186,6 +195,56 @@ def fused_leg(torch, ctx, internal_ifx, master, slot, d_len, d_if, n, recs, stat
     return r
 
 
+def list_leg(torch, ctx, internal_ifx, master, slot, d_len, d_if, n, warmup, reps):
+    """One list call against one fused call per chunk, and against one fused call over everything."""
+    ctx.set_internal_ifindices(internal_ifx)
+    words = (n + 63) // 64
+    lbits = torch.zeros(words, dtype=torch.int64, device="cuda")
+    kbits = torch.zeros(words, dtype=torch.int64, device="cuda")
+    obits = torch.zeros(words, dtype=torch.int64, device="cuda")
+    out = {"internal_ifindices": internal_ifx, "cases": {}}
+    for c in (n // 64, n // 32):
+        assert c % 64 == 0 and n % c == 0
+        K = n // c
+        chunks = [(master[k * c:(k + 1) * c], d_len[k * c:(k + 1) * c], d_if[k * c:(k + 1) * c], k * c // 64)
+                  for k in range(K)]
+        arr = ctx.frame_batches([(f, slot, ln, c, lbits[w:w + c // 64], ifx) for f, ln, ifx, w in chunks])
+        lst = lambda: ctx.verify_frames_batches(arr)   # noqa: E731
+        lst_timed = lambda: ctx.verify_frames_batches_timed(arr)   # noqa: E731
+        one = lambda: ctx.verify_frames_fused_timed(master, slot, d_len, n, obits, ingress_ifindex=d_if)   # noqa: E731
+
+        def calls():
+            for f, ln, ifx, w in chunks:
+                ctx.verify_frames_fused(f, slot, ln, c, kbits[w:w + c // 64], ingress_ifindex=ifx)
+
+        for _ in range(warmup):
+            lst()
+            calls()
+            lst_timed()
+            one()
+        torch.cuda.synchronize()
+        a, b, d, e = [], [], [], []
+        for _ in range(reps):                              # interleaved: all four see the same machine
+            a += region_ms(torch, lst, 1)
+            b += region_ms(torch, calls, 1)
+            d.append(lst_timed())
+            e.append(one())
+        torch.cuda.synchronize()
+        r = {"chunk_frames": c, "chunks": K, "launches": -(-K // 32)}
+        for name, xs in (("list_region_ms", a), ("k_calls_region_ms", b), ("list_dispatch_ms", d),
+                         ("one_call_dispatch_ms", e)):
+            r[name] = round(med(xs), 5)
+            r[name + "_min_max"] = [round(min(xs), 5), round(max(xs), 5)]
+        r["list_region_over_k_calls_region"] = round(med(a) / med(b), 4)
+        r["list_range_below_k_calls_range"] = bool(max(a) < min(b))
+        r["list_dispatch_over_one_call_dispatch"] = round(med(d) / med(e), 4)
+        r["list_dispatch_within_1p10_of_one_call"] = bool(med(d) <= 1.10 * med(e))
+        r["bitmaps_equal"] = bool(torch.equal(lbits, kbits) and torch.equal(lbits, obits))
+        r["frames_passed"] = int(np.unpackbits(lbits.cpu().numpy().view(np.uint8)).sum())
+        out["cases"]["%dx%d" % (K, c)] = r
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=1 << 20)
@@ -196,10 +255,12 @@ def main():
     ap.add_argument("--extract-only", action="store_true", help="A/B runs: the extract kernel alone")
     ap.add_argument("--rx", action="store_true", help="add the direction-aware path (see above)")
     ap.add_argument("--fused", action="store_true", help="add the one-launch path (see above)")
+    ap.add_argument("--list", action="store_true", help="add the frame-batch list (see above)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        name = "frames_fused_probe.json" if args.fused else "frames_rx_probe.json" if args.rx else "frames_probe.json"
+        name = ("frames_list_probe.json" if args.list else "frames_fused_probe.json" if args.fused
+                else "frames_rx_probe.json" if args.rx else "frames_probe.json")
         args.out = os.path.join(ROOT, "profiles", "frames", name)
     args.extract_only |= args.direct   # the other legs want the aligned buffer
     import torch
@@ -316,6 +377,8 @@ def main():
         if args.fused:
             r["fused"] = fused_leg(torch, ctx, internal_ifx, master, slot, d_len, d_if, n, recs, status, bits, act, ver,
                                    egr, args.warmup, reps)
+        if args.list:
+            r["list"] = list_leg(torch, ctx, internal_ifx, master, slot, d_len, d_if, n, args.warmup, reps)
         result["slots"][str(slot)] = r
         del master, buf
     ctx.close()
