@@ -347,6 +347,36 @@ int hfv_verify_records_timed(hfv_ctx *ctx, const void *recs, size_t stride, size
  * hfv_host_register (an RX ring) are read by the kernel in place over PCIe (zero-copy),
  * and a registered pass_bits is written in place. */
 int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_t n, uint64_t *pass_bits);
+/* Frames in HOST memory in, verdict bits out: hfv_verify_frames_fused for a caller whose RX ring is
+ * host memory and who wants the verdicts only (hfv_br_process_host also rewrites the frames and
+ * copies every header window back).  All pointers are host pointers; frames needs no alignment;
+ * ingress_ifindex, status and retried are nullable.  Synchronous: on return
+ * pass_bits[0 .. (n+63)/64) is complete in host memory, and status[0..n) where given.
+ * For every input the outputs are bit-identical to what hfv_verify_frames_fused writes for a device
+ * copy of the same frames, len and ingress_ifindex, under the ctx's key table, keysel and
+ * internal-ifindex set at the time of the call: bits at or past n of the last word are 0, the
+ * bitmap needs no initialisation, no bitmap word or status byte past the end is touched, nothing at
+ * or past frames + n*slot, len + n or ingress_ifindex + n is read, frames is never written, and
+ * the fail-closed rules are those of hfv_verify_frames_fused.
+ * Pageable frames: per chunk of 65536 frames, on two alternating streams, host threads
+ * (HFV_HOST_THREADS) pack the first `window` bytes of each slot into pinned staging, one H2D copy
+ * moves them with len and ingress_ifindex, a windowed kernel parses min(len, slot, window) bytes of
+ * each frame, and one D2H copy brings back two bits per frame (verdict, run again) and, only where
+ * status is given, a byte.  A frame whose headers pass the window (its parse stops at a bound
+ * check while more of the frame lies past the window) is run again with its whole slot, and
+ * *retried receives their number.  window: a multiple of 8 in [64, slot]; 0 means 256, capped at
+ * slot (hfv_br_process_host's rule); the result never depends on it.  The staging belongs to the
+ * ctx: allocated on first use, grown only when the window grows, freed by hfv_ctx_destroy.
+ * Frames inside a buffer registered with hfv_host_register: the full-slot kernel reads them in
+ * place over PCIe (zero-copy), nothing is packed or run again (*retried = 0), and each of len,
+ * ingress_ifindex, status and pass_bits is used in place where it is registered too, else copied
+ * once.
+ * Checks: frames, slot, len and n as hfv_br_process_host; pass_bits non-NULL and 8-byte aligned;
+ * a NULL ctx is -EINVAL even with n == 0, otherwise n == 0 returns 0 and touches nothing.  Like
+ * every data-path call it first stops a running verify service. */
+int hfv_verify_frames_host(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                           const uint32_t *ingress_ifindex, size_t n, size_t window, uint8_t *status,
+                           uint64_t *pass_bits, size_t *retried);
 
 /* ---- resident verify service -----------------------------------------------------------
  * The GPU counterpart of the XDP program staying attached to the interface

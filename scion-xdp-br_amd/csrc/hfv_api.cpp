@@ -178,6 +178,10 @@ int hfv_ctx_destroy(hfv_ctx *ctx)
         if (ctx->brh_hwin[i]) (void)hipHostFree(ctx->brh_hwin[i]);
         if (ctx->brh_dio[i]) (void)hipFree(ctx->brh_dio[i]);
         if (ctx->brh_hio[i]) (void)hipHostFree(ctx->brh_hio[i]);
+        if (ctx->fh_din[i]) (void)hipFree(ctx->fh_din[i]);
+        if (ctx->fh_hin[i]) (void)hipHostFree(ctx->fh_hin[i]);
+        if (ctx->fh_dout[i]) (void)hipFree(ctx->fh_dout[i]);
+        if (ctx->fh_hout[i]) (void)hipHostFree(ctx->fh_hout[i]);
     }
     if (ctx->brh_dstats) (void)hipFree(ctx->brh_dstats);
     if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);

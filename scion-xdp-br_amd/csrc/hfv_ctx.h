@@ -95,6 +95,14 @@ struct hfv_ctx {
     uint8_t *brh_hio[2] = {nullptr, nullptr};   // pinned twin of brh_dio
     uint8_t *brh_hwin[2] = {nullptr, nullptr};  // pinned twin of brh_dwin (packed header windows)
     uint64_t *brh_dstats = nullptr;
+    // frames in host memory (hfv_verify_frames_host): per-stream chunk buffers, pinned and device.
+    // in: len u16[cnt] | ifindex u32[cnt] | packed windows (one H2D copy); out: verdict words |
+    // retry words | status u8[cnt] (one D2H copy).  Grown only when the window grows.
+    size_t fh_win_cap = 0;                      // bytes per frame the in buffers hold
+    uint8_t *fh_hin[2] = {nullptr, nullptr};
+    uint8_t *fh_din[2] = {nullptr, nullptr};
+    uint8_t *fh_hout[2] = {nullptr, nullptr};
+    uint8_t *fh_dout[2] = {nullptr, nullptr};
     // host buffers registered with hfv_host_register (mapped: the kernels can address them)
     struct HostRange {
         uint8_t *host;

@@ -42,45 +42,56 @@ enum : int {
 struct FrameLoc {
     int status;
     uint32_t inf, hf;   // byte offsets of the current InfoField (8 B) / HopField (12 B); valid for status 0
+    // 1: the parse stopped where the next header would pass `end` (a longer `end` might go on);
+    // 0: it succeeded or stopped at a value (EtherType, IHL, IP protocol, SCION version, path
+    // type), which no further byte changes.  Only the windowed kernel of hfv_verify_frames_host
+    // reads it (to tell a header cut by its window from a verdict).
+    uint32_t bound;
 };
+
+HFV_HD FrameLoc frame_bound_stop(FrameLoc loc)
+{
+    loc.bound = 1u;
+    return loc;
+}
 
 // end: data_end - data, i.e. min(frame length, slot)
 template <class R>
 HFV_HD FrameLoc frame_locate(const R &r, int end)
 {
-    FrameLoc loc = {kFrameNotScion, 0u, 0u};
+    FrameLoc loc = {kFrameNotScion, 0u, 0u, 0u};
     // parse_underlay (parser.h:45-114)
     int off = 14;
-    if (off > end) return loc;
+    if (off > end) return frame_bound_stop(loc);
     const uint32_t proto = r.u16(12);
     if (proto == 0x0008u) {          // ETH_P_IP, as the little-endian load of the wire bytes
         off += 20;
-        if (off > end) return loc;
+        if (off > end) return frame_bound_stop(loc);
         const int skip = 4 * (int)(r.u8(14) & 0x0fu) - 20;
         if (skip < 0 || skip > 40) return loc;
         off += skip;
         if (r.u8(14 + 9) != 17u) return loc;
     } else if (proto == 0xdd86u) {   // ETH_P_IPV6
         off += 40;
-        if (off > end) return loc;
+        if (off > end) return frame_bound_stop(loc);
         if (r.u8(14 + 6) != 17u) return loc;
     } else {
         return loc;
     }
     off += 8;                        // UDP
-    if (off > end) return loc;
+    if (off > end) return frame_bound_stop(loc);
     // parse_scion (parser.h:118-148)
     loc.status = kFrameParseError;
     const int sc = off;
     off += 28;                       // common header + destination and source ISD-AS
-    if (off > end) return loc;
+    if (off > end) return frame_bound_stop(loc);
     if ((r.u8(sc) >> 4) != 0u) {
         loc.status = kFrameNotImplemented;
         return loc;
     }
     const uint32_t haddr = r.u8(sc + 9);
     off += 8 + 4 * (int)((haddr >> 2) & 0x2u) + 4 * (int)((haddr >> 6) & 0x2u);
-    if (off > end) return loc;
+    if (off > end) return frame_bound_stop(loc);
     if (r.u8(sc + 8) != 1u) {        // SC_PATH_TYPE_SCION
         loc.status = kFrameNotImplemented;
         return loc;
@@ -88,21 +99,21 @@ HFV_HD FrameLoc frame_locate(const R &r, int end)
     // parse_scion_path (parser.h:153-204)
     const int meta = off;
     off += 4;
-    if (off > end) return loc;
+    if (off > end) return frame_bound_stop(loc);
     const uint32_t h_meta = __builtin_bswap32(r.u32(meta));
     const uint32_t seg0 = (h_meta >> 12) & 0x3fu, seg1 = (h_meta >> 6) & 0x3fu, seg2 = h_meta & 0x3fu;
     const uint32_t num_inf = (seg0 > 0) + (seg1 > 0) + (seg2 > 0);
     const uint32_t curr_inf = (h_meta >> 30) & 0x03u, curr_hf = (h_meta >> 24) & 0x3fu;
     int inf = off + (int)curr_inf * 8;
     loc.inf = (uint32_t)inf;
-    if (inf + 8 > end) return loc;
+    if (inf + 8 > end) return frame_bound_stop(loc);
     if (curr_inf + 1 < num_inf) {
         inf += 8;
-        if (inf + 8 > end) return loc;
+        if (inf + 8 > end) return frame_bound_stop(loc);
     }
     const int hf = off + (int)num_inf * 8 + (int)curr_hf * 12;
     loc.hf = (uint32_t)hf;
-    if (hf + 12 > end) return loc;
+    if (hf + 12 > end) return frame_bound_stop(loc);
     loc.status = kFrameOk;
     return loc;
 }

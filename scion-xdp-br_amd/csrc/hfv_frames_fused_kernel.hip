@@ -2,7 +2,9 @@
 // (hfv_verify_frames_fused): the parse of k_extract_records and the hop-field CMAC of the verify
 // kernels in one kernel, with no record in between.  k_verify_frames takes one batch;
 // k_verify_frames_list (further down; hfv_verify_frames_batches) takes a list of batches and runs
-// the same tile body (fused_tile) over all of their tiles.
+// the same tile body (fused_tile) over all of their tiles; k_verify_frames_win
+// (hfv_verify_frames_host) runs it over packed header windows and also says which frames the window
+// left undecided.
 //
 // k_verify_frames has one lane per frame and a 64-frame tile per wave at a time.  Per tile it
 // stages the first kFrWin bytes of the tile's frames into the wave's LDS rows exactly as the
@@ -61,6 +63,15 @@
 #ifndef HFV_MUT_FUSED
 #define HFV_MUT_FUSED 0
 #endif
+// HFV_MUT_HOSTWIN=N (make hostwin; 0: the product): one wrong step of hfv_verify_frames_host, which
+// tests/test_gpu_frames_hostmem.py must fail on.  1 and 3 sit in the windowed tile body below, 2 in
+// the host's second run (hfv_host_path.cpp).  Every one only masks or indexes wrongly.
+//   1  a bound stop at the window is reported as final: the frame is never run again
+//   2  the second run's verdict lands on the frame's index within the bounce chunk, not its own
+//   3  the retry word of a chunk's last, partial tile votes with all 64 lanes
+#ifndef HFV_MUT_HOSTWIN
+#define HFV_MUT_HOSTWIN 0
+#endif
 
 namespace hfv {
 
@@ -75,12 +86,22 @@ static __shared__ uint32_t s_fu_next;   // the block's tile queue head
 // where status is not null.  all_external: no frame of the batch is internal, whatever ifindex
 // holds.  Every argument but lane and l is wave-uniform.  Shared by k_verify_frames (Batch =
 // FusedArgs) and k_verify_frames_list (FrameBatchCur).
-template <int KEYSEL, int WIN, class Batch>
+//
+// WINDOWED (k_verify_frames_win): a.frames holds packed header windows, `window` bytes per frame at a
+// stride of `window`, and a.slot is still what the lengths are clamped to.  The parse runs with
+// min(len, slot, window), so it reads no byte at or past the window; a frame it leaves undecided (a
+// bound stop, more of the frame past the window) votes into retry[t], a second ballot word stored
+// whole like the verdict word, and its verdict bit is 0 (its status is not kFrameOk).
+template <int KEYSEL, int WIN, bool WINDOWED = false, class Batch>
 __device__ __forceinline__ void fused_tile(const Batch &a, const RxSet &set, bool all_external, uint64_t t, uint32_t nf,
                                            uint32_t nvote, uint32_t *rows, uint32_t lane, const UniformKey &ukey,
-                                           const Lane &l)
+                                           const Lane &l, uint32_t window = 0u, unsigned long long *retry = nullptr)
 {
     const uint64_t base = t * 64;
+    const auto stride = [&] {   // bytes between the rows of a.frames
+        if constexpr (WINDOWED) return (uint64_t)window;
+        else return a.slot;
+    }();
     // the lane's own frame (lanes past the last frame: that frame again, never counted), its
     // data_end - data = min(len, slot) and its receiving ifindex: asked for ahead of the rows and
     // pinned once the row loads are issued, as in k_extract_records
@@ -96,7 +117,7 @@ __device__ __forceinline__ void fused_tile(const Batch &a, const RxSet &set, boo
         for (int r = 0; r < kFrC; ++r) {
             uint32_t fr = r * (64 / kFrC) + fr_of;
             if (fr >= nf) fr = nf - 1;
-            pre[r] = *reinterpret_cast<const fr_v4u *>(a.frames + (base + fr) * a.slot + 16u * ch);
+            pre[r] = *reinterpret_cast<const fr_v4u *>(a.frames + (base + fr) * stride + 16u * ch);
         }
         asm volatile("" : "+v"(end), "+v"(ifx));   // no instruction: the length and ifindex loads are complete here
 #pragma unroll
@@ -107,8 +128,10 @@ __device__ __forceinline__ void fused_tile(const Batch &a, const RxSet &set, boo
         rows[lane * kFrRow + kFrWin / 4] = 0u;   // the lane's pad dword: read (and shifted out) by u32(124)
         wave_sync();
     }
-    const FrameReader<WIN> rd = {rows + lane * kFrRow, a.frames + i * a.slot};
-    const FrameLoc loc = frame_locate(rd, (int)end);
+    const FrameReader<WIN> rd = {rows + lane * kFrRow, a.frames + i * stride};
+    uint32_t pend = end;   // what the parse may read: the frame, or no more of it than was packed
+    if constexpr (WINDOWED) pend = window < end ? window : end;
+    const FrameLoc loc = frame_locate(rd, (int)pend);
     uint32_t w[5] = {0u, 0u, 0u, 0u, 0u};   // InfoField bytes 0-7, HopField bytes 0-11
     if (loc.status == kFrameOk) {
         w[0] = rd.u32((int)loc.inf);
@@ -138,6 +161,12 @@ __device__ __forceinline__ void fused_tile(const Batch &a, const RxSet &set, boo
     const uint32_t e0 = __builtin_amdgcn_alignbit(w[4], w[3], 16), e1 = w[4] >> 16;   // mac0..3, mac4..5
     const unsigned long long m = __ballot(ok && t0 == e0 && ((t1 ^ e1) & 0xffffu) == 0);
     if (lane == 0) a.bits[t] = m;
+    if constexpr (WINDOWED) {
+        // HFV_MUT_HOSTWIN 1: never undecided; 3: a partial tile's lanes past nf vote with the clamped frame
+        const bool again = HFV_MUT_HOSTWIN != 1 && loc.bound != 0u && end > window;
+        const unsigned long long ra = __ballot((HFV_MUT_HOSTWIN == 3 || lane < nvote) && again);
+        if (lane == 0) retry[t] = ra;
+    }
     if (a.status && lane < nf) a.status[i] = (uint8_t)loc.status;
     if constexpr (WIN > 0) wave_sync();   // the rows are free for the wave's next tile
 }
@@ -165,6 +194,35 @@ __global__ __launch_bounds__(fused_waves(KEYSEL) * 64) void k_verify_frames(cons
         const uint64_t left = a.n - t * 64;
         const uint32_t nf = left < 64 ? (uint32_t)left : 64u;
         fused_tile<KEYSEL, WIN>(a, a.set, false, t, nf, nf, rows, lane, ukey, l);
+    }
+}
+
+// Packed header windows (hfv_verify_frames_host's pageable path): k_verify_frames with the rows at a
+// stride of a.window bytes and the parse clamped to the window (fused_tile, WINDOWED).  Prologue,
+// grid, tile dealing and LDS budgets are k_verify_frames' own.
+template <int KEYSEL, int WIN>
+__global__ __launch_bounds__(fused_waves(KEYSEL) * 64) void k_verify_frames_win(const FusedWinArgs a)
+{
+    constexpr int kW = fused_waves(KEYSEL);
+    __shared__ uint32_t s_rows[WIN > 0 ? kW * 64 * kFrRow : 1];
+    fill_ttab<3>();
+    if constexpr (KEYSEL == HFV_KEYSEL_IFID) fill_keys5<3>(a.f.tab, kW * 64);
+    if (threadIdx.x == 0) s_fu_next = 0u;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const uint64_t ntiles = (a.f.n + 63) / 64;
+    const uint64_t tb0 = ntiles * blockIdx.x / gridDim.x, tb1 = ntiles * (blockIdx.x + 1) / gridDim.x;
+    uint32_t *rows = s_rows + (WIN > 0 ? wib * 64 * kFrRow : 0);
+    const UniformKey ukey(a.f.key0, a.f.key0_ok);
+    const Lane l = lane_bases3();
+    for (;;) {
+        uint32_t c = 0;
+        if (lane == 0) c = atomicAdd(&s_fu_next, 1u);
+        const uint64_t t = tb0 + wave_uniform(c);
+        if (t >= tb1) break;   // wave-uniform; no block barrier below
+        const uint64_t left = a.f.n - t * 64;
+        const uint32_t nf = left < 64 ? (uint32_t)left : 64u;
+        fused_tile<KEYSEL, WIN, true>(a.f, a.f.set, false, t, nf, nf, rows, lane, ukey, l, a.window, a.retry);
     }
 }
 
@@ -295,6 +353,31 @@ int launch_verify_frames(const LaunchGeom &g, int keysel, FusedArgs a, const Dev
     if (g.batch_grid_cap && g.batch_grid_cap < blocks) blocks = g.batch_grid_cap;   // test build only
     hipExtLaunchKernelGGL(k, dim3((unsigned)(blocks ? blocks : 1)), dim3((unsigned)waves * 64), 0, (hipStream_t)stream,
                           (hipEvent_t)ev_start, (hipEvent_t)ev_stop, 0u, a);
+    return (int)hipGetLastError();
+}
+
+int launch_verify_frames_win(const LaunchGeom &g, int keysel, FusedWinArgs a, const DevKeyTable *host_keys,
+                             void *stream)
+{
+    const KeyPrologue pro = key_prologue(host_keys);
+    memcpy(a.f.key0, pro.key0, sizeof a.f.key0);
+    a.f.key0_ok = pro.key0_ok;
+    if (!a.f.ifindex || a.f.set.n == 0) {   // every frame is external
+        a.f.ifindex = nullptr;
+        a.f.set.n = 0;
+    }
+    // the 16-byte staging loads read kFrWin bytes of every packed row
+    const bool can_stage = a.window >= (uint32_t)kFrWin && a.window % 16 == 0 && ((uintptr_t)a.f.frames & 15) == 0;
+    const bool ifid = keysel == HFV_KEYSEL_IFID;
+    using K = void (*)(const FusedWinArgs);
+    const K k = ifid ? (can_stage ? k_verify_frames_win<HFV_KEYSEL_IFID, kFrWin> : k_verify_frames_win<HFV_KEYSEL_IFID, 0>)
+                     : (can_stage ? k_verify_frames_win<HFV_KEYSEL_ZERO, kFrWin> : k_verify_frames_win<HFV_KEYSEL_ZERO, 0>);
+    const uint64_t waves = (uint64_t)fused_waves(keysel);
+    const uint64_t tiles = (a.f.n + 63) / 64;
+    uint64_t blocks = (tiles + waves - 1) / waves;   // the grid of launch_verify_frames
+    if (blocks > (uint64_t)g.num_cus) blocks = (uint64_t)g.num_cus;
+    if (g.batch_grid_cap && g.batch_grid_cap < blocks) blocks = g.batch_grid_cap;   // test build only
+    hipLaunchKernelGGL(k, dim3((unsigned)(blocks ? blocks : 1)), dim3((unsigned)waves * 64), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
 

@@ -1,6 +1,7 @@
 // hfv_host_path.cpp -- the entry points that take frames or records in host memory
-// (hfv_br_process_host, hfv_verify_records_host, hfv_host_register), their staging workers
-// (host thread pool, NUMA pinning), and the router stage of in-library pipelines (hfv_loop.cpp).
+// (hfv_br_process_host, hfv_verify_records_host, hfv_verify_frames_host, hfv_host_register), their
+// staging workers (host thread pool, NUMA pinning), and the router stage of in-library pipelines
+// (hfv_loop.cpp).
 #include <pthread.h>
 #include <stdlib.h>
 
@@ -552,3 +553,250 @@ int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_
 }
 
 }  // extern "C"
+
+// ---- frames in host memory -> verdict bits (hfv_verify_frames_host) ----------------------------
+// HFV_MUT_HOSTWIN: see hfv_frames_fused_kernel.hip (make hostwin; 0 in every product build).
+#ifndef HFV_MUT_HOSTWIN
+#define HFV_MUT_HOSTWIN 0
+#endif
+
+// Frames per chunk: a multiple of 64, so that no bitmap word straddles two chunks.
+static const size_t kFhChunk = (size_t)1 << 16;
+#ifdef HFV_TEST_HOOKS
+// hfv_debug_frames_host_chunk: frames per chunk of hfv_verify_frames_host (a multiple of 64, at most
+// the default; 0 restores it), so that a few hundred frames span several chunks and both streams.
+static size_t g_fh_chunk = 0;
+extern "C" int hfv_debug_frames_host_chunk(size_t frames)
+{
+    if ((frames & 63) || frames > kFhChunk) return fail(-EINVAL, "chunk must be a multiple of 64, at most %zu", kFhChunk);
+    g_fh_chunk = frames;
+    return 0;
+}
+static size_t fh_chunk() { return g_fh_chunk ? g_fh_chunk : kFhChunk; }
+#else
+static size_t fh_chunk() { return kFhChunk; }
+#endif
+
+static size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Where a chunk of cnt frames keeps its parts.  In (one H2D copy of `in` bytes): len u16[cnt], the
+// ifindex u32[cnt] (only where the caller gave one), then the rows, each part 16-byte aligned.
+// Out (one D2H copy of `out` bytes): the verdict words, the retry words, then status u8[cnt] (only
+// where wanted).
+struct FhLayout {
+    size_t ifx, rows, in;
+    size_t words, status, out;
+};
+static FhLayout fh_layout(size_t cnt, size_t pitch, bool with_ifx, bool with_status)
+{
+    FhLayout l;
+    l.ifx = up16(cnt * 2);
+    l.rows = l.ifx + (with_ifx ? up16(cnt * 4) : 0);
+    l.in = l.rows + cnt * pitch;
+    l.words = (cnt + 63) / 64;
+    l.status = l.words * 16;
+    l.out = l.status + (with_status ? cnt : 0);
+    return l;
+}
+
+static int fh_buffers(hfv_ctx *ctx, size_t pitch)
+{
+    for (int i = 0; i < 2; ++i) {
+        if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
+        if (!ctx->fh_dout[i]) {
+            const size_t out = fh_layout(kFhChunk, 0, false, true).out;
+            HIP_TRY(hipMalloc((void **)&ctx->fh_dout[i], out));
+            HIP_TRY(hipHostMalloc((void **)&ctx->fh_hout[i], out, hipHostMallocDefault));
+        }
+    }
+    if (ctx->fh_win_cap < pitch) {
+        const size_t in = fh_layout(kFhChunk, pitch, true, false).in;
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(hipStreamSynchronize(ctx->hstream[i]));
+            if (ctx->fh_din[i]) (void)hipFree(ctx->fh_din[i]);
+            if (ctx->fh_hin[i]) (void)hipHostFree(ctx->fh_hin[i]);
+            ctx->fh_din[i] = ctx->fh_hin[i] = nullptr;
+            ctx->fh_win_cap = 0;
+            HIP_TRY(hipMalloc((void **)&ctx->fh_din[i], in));
+            HIP_TRY(hipHostMalloc((void **)&ctx->fh_hin[i], in, hipHostMallocDefault));
+        }
+        ctx->fh_win_cap = pitch;
+    }
+    return 0;
+}
+
+// The launch of one chunk whose parts are on the device as `l` says: the windowed kernel over
+// packed windows (it also writes the chunk's retry words: all zero where window == slot), or, for
+// the second run's whole slots, the full-slot kernel of hfv_verify_frames_fused.
+static int fh_launch(hfv_ctx *ctx, int sl, const FhLayout &l, size_t slot, size_t window, bool whole, bool with_ifx,
+                     bool with_status, size_t cnt)
+{
+    hipStream_t st = ctx->hstream[sl];
+    uint8_t *din = ctx->fh_din[sl], *dout = ctx->fh_dout[sl];
+    return with_tables(ctx, st, "verify_frames_host launch", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
+        FusedWinArgs a;
+        memset(&a, 0, sizeof a);
+        a.f.frames = din + l.rows;
+        a.f.slot = slot;
+        a.f.lens = (const uint16_t *)din;
+        a.f.ifindex = with_ifx ? (const uint32_t *)(din + l.ifx) : nullptr;
+        a.f.n = cnt;
+        a.f.status = with_status ? dout + l.status : nullptr;
+        a.f.bits = (unsigned long long *)dout;
+        a.f.tab = &ds->keys;
+        a.f.set = ctx->rx_set;
+        if (whole) return launch_verify_frames(batch_geom(ctx), ctx->keysel, a.f, &ctx->host_img->keys, st);
+        a.window = (uint32_t)window;
+        a.retry = (unsigned long long *)(dout + l.words * 8);
+        return launch_verify_frames_win(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, st);
+    });
+}
+
+// Zero-copy: the frames lie in a registered (mapped) ring, so the full-slot kernel reads them in
+// place over PCIe and nothing is packed or run again.  Each of len, ifindex, status and the bitmap
+// is used in place where it is registered too, else it goes through zc_meta with one copy.
+static int verify_frames_zero_copy(hfv_ctx *ctx, const uint8_t *dframes, size_t slot, const uint16_t *len,
+                                   const uint32_t *ifx, size_t n, uint8_t *status, uint64_t *pass_bits)
+{
+    hipStream_t st = ctx->stream;
+    const size_t words = (n + 63) / 64;
+    const uint16_t *dlen = (const uint16_t *)host_dev_ptr(ctx, len, n * 2);
+    const uint32_t *difx = ifx ? (const uint32_t *)host_dev_ptr(ctx, ifx, n * 4) : nullptr;
+    uint8_t *dstatus = status ? host_dev_ptr(ctx, status, n) : nullptr;
+    uint64_t *dbits = (uint64_t *)host_dev_ptr(ctx, pass_bits, words * 8);
+    const size_t o_ifx = words * 8, o_len = o_ifx + n * 4, o_status = o_len + n * 2, need = o_status + n;
+    if ((!dlen || (ifx && !difx) || (status && !dstatus) || !dbits) && ctx->zc_cap < need) {
+        if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
+        ctx->zc_meta = nullptr;
+        ctx->zc_cap = 0;
+        HIP_TRY(hipMalloc((void **)&ctx->zc_meta, need));
+        ctx->zc_cap = need;
+    }
+    uint8_t *m = ctx->zc_meta;
+    const bool cp_bits = !dbits, cp_status = status && !dstatus;
+    if (!dlen) {
+        HIP_TRY(hipMemcpyAsync(m + o_len, len, n * 2, hipMemcpyHostToDevice, st));
+        dlen = (const uint16_t *)(m + o_len);
+    }
+    if (ifx && !difx) {
+        HIP_TRY(hipMemcpyAsync(m + o_ifx, ifx, n * 4, hipMemcpyHostToDevice, st));
+        difx = (const uint32_t *)(m + o_ifx);
+    }
+    if (cp_bits) dbits = (uint64_t *)m;
+    if (cp_status) dstatus = m + o_status;
+    int rc = with_tables(ctx, st, "verify_frames_host launch (zero-copy)", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
+        FusedArgs a;
+        memset(&a, 0, sizeof a);
+        a.frames = dframes;
+        a.slot = slot;
+        a.lens = dlen;
+        a.ifindex = difx;
+        a.n = n;
+        a.status = dstatus;
+        a.bits = (unsigned long long *)dbits;
+        a.tab = &ds->keys;
+        a.set = ctx->rx_set;
+        return launch_verify_frames(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, st);
+    });
+    if (rc) return rc;
+    if (cp_bits) HIP_TRY(hipMemcpyAsync(pass_bits, dbits, words * 8, hipMemcpyDeviceToHost, st));
+    if (cp_status) HIP_TRY(hipMemcpyAsync(status, dstatus, n, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return 0;
+}
+
+extern "C" int hfv_verify_frames_host(hfv_ctx *ctx, const uint8_t *frames, size_t slot, const uint16_t *len,
+                                      const uint32_t *ingress_ifindex, size_t n, size_t window, uint8_t *status,
+                                      uint64_t *pass_bits, size_t *retried)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    if (!frames || !len || !pass_bits) return fail(-EINVAL, "null buffer");
+    if (slot < 64 || (slot & 7) || slot > 65535 * 8) return fail(-EINVAL, "slot must be >= 64 and a multiple of 8");
+    if (window == 0) window = slot < 256 ? slot : 256;
+    if (window < 64 || (window & 7) || window > slot) return fail(-EINVAL, "window must be a multiple of 8 in [64, slot]");
+    if ((uintptr_t)pass_bits & 7) return fail(-EINVAL, "bitmap must be 8-byte aligned");
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    if (retried) *retried = 0;
+    if (const uint8_t *dframes = host_dev_ptr(ctx, frames, n * slot))
+        return verify_frames_zero_copy(ctx, dframes, slot, len, ingress_ifindex, n, status, pass_bits);
+    int rc = fh_buffers(ctx, window);
+    if (rc) return rc;
+    const bool with_ifx = ingress_ifindex != nullptr, with_status = status != nullptr;
+    const size_t chunk = fh_chunk(), nchunks = (n + chunk - 1) / chunk;
+    // Chunk c is packed by the host threads while chunk c - 1's copy and kernel run on the other
+    // stream; chunk c - 2 (same stream, same buffers) is retired first.
+    std::vector<size_t> again;   // the frames to run again, in order
+    size_t first_of[2] = {0, 0}, cnt_of[2] = {0, 0};
+    for (size_t c = 0; c < nchunks + 2; ++c) {
+        const int sl = (int)(c & 1);
+        hipStream_t st = ctx->hstream[sl];
+        if (c >= 2) {
+            HIP_TRY(hipStreamSynchronize(st));
+            const size_t f = first_of[sl], cnt = cnt_of[sl];
+            const FhLayout l = fh_layout(cnt, window, with_ifx, with_status);
+            const uint64_t *w = (const uint64_t *)ctx->fh_hout[sl];
+            memcpy(pass_bits + f / 64, w, l.words * 8);
+            if (with_status) memcpy(status + f, ctx->fh_hout[sl] + l.status, cnt);
+            for (size_t k = 0; k < l.words; ++k) {
+                uint64_t r = w[l.words + k];
+                const size_t left = cnt - k * 64;
+                if (left < 64 && (r >> left)) return fail(-EIO, "retry word %zu marks frames past the chunk's %zu", k, cnt);
+                for (; r; r &= r - 1) again.push_back(f + k * 64 + (size_t)__builtin_ctzll(r));
+            }
+        }
+        if (c >= nchunks) continue;
+        const size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
+        const FhLayout l = fh_layout(cnt, window, with_ifx, with_status);
+        uint8_t *hin = ctx->fh_hin[sl];
+        memcpy(hin, len + first, cnt * 2);
+        if (with_ifx) memcpy(hin + l.ifx, ingress_ifindex + first, cnt * 4);
+        copy_rows(hin + l.rows, window, frames + first * slot, slot, window, cnt);
+        HIP_TRY(hipMemcpyAsync(ctx->fh_din[sl], hin, l.in, hipMemcpyHostToDevice, st));
+        rc = fh_launch(ctx, sl, l, slot, window, /*whole=*/false, with_ifx, with_status, cnt);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->fh_hout[sl], ctx->fh_dout[sl], l.out, hipMemcpyDeviceToHost, st));
+        first_of[sl] = first;
+        cnt_of[sl] = cnt;
+    }
+    if (retried) *retried = again.size();
+    if (again.empty()) return 0;
+    // The second run: the marked frames' whole slots, gathered into the pinned staging chunk by
+    // chunk, through the full-slot kernel; each verdict into the frame's own bit, each status into
+    // its own byte.
+    rc = fh_buffers(ctx, slot);
+    if (rc) return rc;
+    for (size_t done = 0; done < again.size(); done += chunk) {
+        const size_t cnt = again.size() - done < chunk ? again.size() - done : chunk;
+        const size_t *idx = again.data() + done;
+        const FhLayout l = fh_layout(cnt, slot, with_ifx, with_status);
+        uint8_t *hin = ctx->fh_hin[0];
+        uint16_t *blen = (uint16_t *)hin;
+        uint32_t *bifx = (uint32_t *)(hin + l.ifx);
+        for (size_t k = 0; k < cnt; ++k) {
+            blen[k] = len[idx[k]];
+            if (with_ifx) bifx[k] = ingress_ifindex[idx[k]];
+        }
+        parallel_rows(cnt, [=](size_t a, size_t b) {
+            for (size_t k = a; k < b; ++k) memcpy(hin + l.rows + k * slot, frames + idx[k] * slot, slot);
+        });
+        hipStream_t st = ctx->hstream[0];
+        HIP_TRY(hipMemcpyAsync(ctx->fh_din[0], hin, l.in, hipMemcpyHostToDevice, st));
+        rc = fh_launch(ctx, 0, l, slot, slot, /*whole=*/true, with_ifx, with_status, cnt);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->fh_hout[0], ctx->fh_dout[0], l.out, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const uint64_t *w = (const uint64_t *)ctx->fh_hout[0];
+        for (size_t k = 0; k < cnt; ++k) {
+            const size_t j = HFV_MUT_HOSTWIN == 2 ? k : idx[k];
+            const uint64_t bit = (uint64_t)1 << (j & 63);
+            if ((w[k / 64] >> (k & 63)) & 1)
+                pass_bits[j / 64] |= bit;
+            else
+                pass_bits[j / 64] &= ~bit;
+            if (with_status) status[j] = ctx->fh_hout[0][l.status + k];
+        }
+    }
+    return 0;
+}

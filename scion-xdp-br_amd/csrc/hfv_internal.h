@@ -355,6 +355,22 @@ struct FusedArgs {
 int launch_verify_frames(const LaunchGeom &g, int keysel, FusedArgs a, const DevKeyTable *host_keys, void *stream,
                          void *ev_start = nullptr, void *ev_stop = nullptr);
 
+// The same over packed header windows (hfv_verify_frames_host, k_verify_frames_win): f.frames holds
+// the first `window` bytes of each frame at a stride of `window` bytes (a multiple of 8 in
+// [64, f.slot]), f.slot stays the caller's slot (lengths are clamped to it) and the parse runs
+// with min(len, slot, window).  A frame whose parse stops at a bound check while min(len, slot) >
+// window is undecided: its verdict bit is 0, its status that of the cut parse, and its bit in
+// retry[tile] is set for the host to run it again with its whole slot.  retry has the bitmap's
+// words and is written whole, like it: bits at or past f.n are 0.  The staged kernel where window
+// >= 128, window % 16 == 0 and f.frames is 16-byte aligned.
+struct FusedWinArgs {
+    FusedArgs f;
+    uint32_t window;
+    unsigned long long *retry;
+};
+int launch_verify_frames_win(const LaunchGeom &g, int keysel, FusedWinArgs a, const DevKeyTable *host_keys,
+                             void *stream);
+
 // A list of frame batches in one launch (hfv_verify_frames_batches, k_verify_frames_list): up to
 // kFrameBatchMax batches, their descriptors and the running tile count cum[] (batch j = global
 // tiles [cum[j], cum[j+1]), cum[nb] = total) in the one by-value kernel argument, beside what

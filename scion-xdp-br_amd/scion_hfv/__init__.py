@@ -130,6 +130,7 @@ def lib():
         "hfv_host_unregister": (i32, [vp, vp]),
         "hfv_cmac_tags": (i32, [vp, vp, vp, sz, vp, vp]),
         "hfv_verify_records_host": (i32, [vp, vp, sz, sz, vp]),
+        "hfv_verify_frames_host": (i32, [vp, vp, sz, vp, vp, sz, sz, vp, vp, ctypes.POINTER(sz)]),
         "hfv_service_start": (i32, [vp, u32]),
         "hfv_service_submit": (i32, [vp, vp, sz, sz, vp, ctypes.POINTER(u64)]),
         "hfv_service_submitv": (i32, [vp, vp, sz, ctypes.POINTER(u64)]),
@@ -907,6 +908,22 @@ class Ctx:
     # host buffers (pinned staging, H2D/kernel/D2H overlapped)
     def verify_records_host(self, recs, n, pass_bits, stride=REC_SIZE):
         _check(lib().hfv_verify_records_host(self._h, _ptr(recs), stride, n, _ptr(pass_bits)))
+
+    def verify_frames_host(self, frames, slot, lens, n, pass_bits, ingress_ifindex=None, status=None, window=0):
+        """hfv_verify_frames_host: frames in host memory (numpy arrays) to verdict bits, the bits and
+        status of verify_frames_fused.  Only the first `window` bytes of each slot are copied up (0:
+        256, capped at slot), two bits per frame come back; frames in a registered buffer
+        (host_register) are read in place.  Returns the number of frames run again with their whole
+        slot."""
+        retried = ctypes.c_size_t(0)
+        _check(lib().hfv_verify_frames_host(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n, window,
+                                            _ptr(status), _ptr(pass_bits), ctypes.byref(retried)))
+        return retried.value
+
+    @staticmethod
+    def debug_frames_host_chunk(frames):
+        """Test-only: frames per chunk of verify_frames_host (a multiple of 64; 0 = the default)."""
+        _check(lib().hfv_debug_frames_host_chunk(ctypes.c_size_t(frames)))
 
 
 # ---- full BR path (config 4): router tables --------------------------------------------------
