@@ -15,6 +15,75 @@
 // Compact staging record of the host path: INF (8 B) at 0, HF (12 B) at 8, 4 B pad.
 static constexpr size_t kHostRec = 24;
 
+// Records per chunk of hfv_verify_records_host (a multiple of 64, so that no bitmap word straddles two
+// chunks), frames per chunk and per retry round of hfv_br_process_host, and the row count below which
+// parallel_rows runs inline.  kBrChunk is also the layout constant of brh_dio / brh_hio / brh_dwin.
+static const size_t kRecChunk = (size_t)1 << 18;
+static const size_t kBrChunk = (size_t)1 << 16;
+static const size_t kInlineRows = 8192;
+
+// HFV_MUT_HOSTCHUNK (make hostchunk; 0 in every product build): one deliberately wrong step of the
+// chunk pipelines below, each in bounds of every buffer and with every synchronisation kept:
+//   1  records: a retired chunk's bitmap is copied to the other slot's pending_first (cut at the end
+//      of the caller's bitmap)
+//   2  records: a ragged chunk copies back cnt / 64 words (floor)
+//   3  records: chunks after the first gather from recs + first * kHostRec instead of first * stride
+//      (in bounds for stride >= kHostRec)
+//   4  router: a retired chunk's results go to first_of[sl ^ 1] (cut at frame n)
+//   5  router: the verdict counters are zeroed before every chunk instead of once per call (after the
+//      other stream has drained, so that the loss is the same in every run)
+//   6  router: a retry round's results are scattered through idx[cnt - 1 - k]
+// tests/test_gpu_host_chunks.py must fail on every one.
+#ifndef HFV_MUT_HOSTCHUNK
+#define HFV_MUT_HOSTCHUNK 0
+#endif
+
+#ifdef HFV_TEST_HOOKS
+// hfv_debug_records_host_chunk / _br_host_chunk / _host_inline_rows: the three counts above made small,
+// so that a few hundred records or frames span several chunks, reuse both stream slots, fill several
+// retry rounds and go through the host pool's partition; 0 restores the default.  The staging buffers
+// keep their full size: only the counts change.  hfv_debug_host_chunk_counts: what the last
+// hfv_verify_records_host / hfv_br_process_host call of the process ran (read-only): chunks launched in
+// the first pass, retry rounds, frames retried, chunks that reused a slot within the call.
+static size_t g_rec_chunk = 0, g_br_chunk = 0, g_inline_rows = 0;
+static uint64_t g_hc_counts[4] = {0, 0, 0, 0};
+extern "C" int hfv_debug_records_host_chunk(size_t records)
+{
+    if ((records & 63) || records > kRecChunk) return fail(-EINVAL, "chunk must be a multiple of 64, at most %zu", kRecChunk);
+    g_rec_chunk = records;
+    return 0;
+}
+extern "C" int hfv_debug_br_host_chunk(size_t frames)
+{
+    if (frames > kBrChunk) return fail(-EINVAL, "chunk must be at most %zu", kBrChunk);
+    g_br_chunk = frames;
+    return 0;
+}
+extern "C" int hfv_debug_host_inline_rows(size_t rows)
+{
+    g_inline_rows = rows;
+    return 0;
+}
+extern "C" int hfv_debug_host_chunk_counts(uint64_t out[4])
+{
+    if (!out) return fail(-EINVAL, "null buffer");
+    memcpy(out, g_hc_counts, sizeof g_hc_counts);
+    return 0;
+}
+static size_t rec_chunk() { return g_rec_chunk ? g_rec_chunk : kRecChunk; }
+static size_t br_chunk() { return g_br_chunk ? g_br_chunk : kBrChunk; }
+static size_t inline_rows() { return g_inline_rows ? g_inline_rows : kInlineRows; }
+static void hc_reset() { memset(g_hc_counts, 0, sizeof g_hc_counts); }
+static void hc_add(int k, uint64_t v) { g_hc_counts[k] += v; }
+#else
+static size_t rec_chunk() { return kRecChunk; }
+static size_t br_chunk() { return kBrChunk; }
+static size_t inline_rows() { return kInlineRows; }
+static void hc_reset() {}
+static void hc_add(int, uint64_t) {}
+#endif
+enum { kHcChunks = 0, kHcRounds = 1, kHcRetried = 2, kHcReuses = 3 };
+
 // Host threads for staging copies: HFV_HOST_THREADS, default min(8, cores).
 static int host_threads()
 {
@@ -169,11 +238,11 @@ static HostPool &host_pool()
     return pool;
 }
 
-// fn(a, b) over [0, n) split into host_threads() contiguous parts (inline below 8192 items).
+// fn(a, b) over [0, n) split into host_threads() contiguous parts (inline below kInlineRows items).
 template <class F>
 static void parallel_rows(size_t n, F fn)
 {
-    if (host_threads() <= 1 || n < 8192) {
+    if (host_threads() <= 1 || n < inline_rows()) {
         fn((size_t)0, n);
         return;
     }
@@ -201,11 +270,10 @@ static void copy_rows(uint8_t *dst, size_t dpitch, const uint8_t *src, size_t sp
     });
 }
 
-// Windowed host path.  Per chunk of kBrChunk frames, on alternating streams: strided H2D of
+// Windowed host path.  Per chunk of br_chunk() frames, on alternating streams: strided H2D of
 // the windows + metadata, the kernel (stride = window, lengths clamped to the caller's slot),
 // strided D2H of the rewritten windows + results.  Then frames marked HFV_BR_ACTION_RETRY
 // (headers beyond the window) go through again with whole slots.
-static const size_t kBrChunk = (size_t)1 << 16;
 static const size_t kBrStatWords = HFV_BR_STATS_IFINDEX * 2 * HFV_BR_COUNTERS;
 
 // The device verdict counters of one host-path call: allocated on first use, zeroed on `st`.
@@ -368,40 +436,52 @@ int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16
     if (window < 64 || (window & 7) || window > slot) return fail(-EINVAL, "window must be a multiple of 8 in [64, slot]");
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
+    hc_reset();
     uint8_t *dframes = host_dev_ptr(ctx, frames, n * slot);
     if (dframes) return br_zero_copy(ctx, dframes, slot, len, ingress_ifindex, n, action, verdict, egress_ifindex, stats);
     int rc = brh_buffers(ctx, window > slot ? slot : window);
     if (!rc) rc = brh_stats_buffer(ctx, ctx->hstream[0]);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->hstream[0]));
-    size_t nchunks = (n + kBrChunk - 1) / kBrChunk;
+    const size_t chunk = br_chunk(), nchunks = (n + chunk - 1) / chunk;
+    hc_add(kHcChunks, nchunks);
     size_t first_of[2] = {0, 0}, cnt_of[2] = {0, 0};
     for (size_t c = 0; c < nchunks + 2; ++c) {
         int sl = (int)(c & 1);
         if (c >= 2) {
             HIP_TRY(hipStreamSynchronize(ctx->hstream[sl]));
-            size_t f = first_of[sl];
-            brh_results(ctx, sl, frames + f * slot, slot, window, cnt_of[sl], action + f, verdict + f,
-                        egress_ifindex + f);
+            size_t f = first_of[sl], fcnt = cnt_of[sl];
+            if (HFV_MUT_HOSTCHUNK == 4) {
+                f = first_of[sl ^ 1];
+                if (fcnt > n - f) fcnt = n - f;
+            }
+            brh_results(ctx, sl, frames + f * slot, slot, window, fcnt, action + f, verdict + f, egress_ifindex + f);
         }
         if (c >= nchunks) continue;
-        size_t first = c * kBrChunk, cnt = n - first < kBrChunk ? n - first : kBrChunk;
+        if (c >= 2) hc_add(kHcReuses, 1);
+        size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
+        if (HFV_MUT_HOSTCHUNK == 5 && c >= 1) {
+            HIP_TRY(hipStreamSynchronize(ctx->hstream[sl ^ 1]));
+            HIP_TRY(hipMemsetAsync(ctx->brh_dstats, 0, kBrStatWords * 8, ctx->hstream[sl]));
+        }
         rc = brh_chunk(ctx, sl, frames + first * slot, slot, slot, window, len + first, ingress_ifindex + first, cnt);
         if (rc) return rc;
         first_of[sl] = first;
         cnt_of[sl] = cnt;
     }
-    // frames whose headers did not fit the window: whole slots, in chunks, through a bounce buffer
+    // frames whose headers did not fit the window: whole slots, in rounds, through a bounce buffer
     size_t nretry = 0;
     for (size_t i = 0; i < n; ++i) nretry += action[i] == HFV_BR_ACTION_RETRY;
+    hc_add(kHcRetried, nretry);
     if (nretry) {
         rc = brh_buffers(ctx, slot);
         if (rc) return rc;
         uint8_t *bounce = nullptr;
-        size_t cap = nretry < kBrChunk ? nretry : kBrChunk;
-        HIP_TRY(hipHostMalloc((void **)&bounce, cap * slot + cap * 8, hipHostMallocDefault));
-        uint16_t *blen = (uint16_t *)(bounce + cap * slot);
-        uint32_t *bif = (uint32_t *)(bounce + cap * slot + cap * 2);
+        size_t cap = nretry < chunk ? nretry : chunk;
+        // cap slots (slot is a multiple of 8), then ifindex u32[cap], then len u16[cap]: each part aligned
+        HIP_TRY(hipHostMalloc((void **)&bounce, cap * slot + cap * 4 + cap * 2, hipHostMallocDefault));
+        uint32_t *bif = (uint32_t *)(bounce + cap * slot);
+        uint16_t *blen = (uint16_t *)(bounce + cap * slot + cap * 4);
         size_t *idx = (size_t *)malloc(cap * sizeof(size_t));
         size_t i = 0;
         while (rc == 0 && i < n) {
@@ -414,10 +494,13 @@ int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16
                 idx[cnt++] = i;
             }
             if (!cnt) break;
-            rc = brh_chunk(ctx, 0, bounce, slot, slot, slot, blen, bif, cnt);
+            hc_add(kHcRounds, 1);
+            if (HFV_MUT_HOSTCHUNK == 5 && hipMemsetAsync(ctx->brh_dstats, 0, kBrStatWords * 8, ctx->hstream[0]) != hipSuccess)
+                rc = fail(-EIO, "retry chunk");
+            if (rc == 0) rc = brh_chunk(ctx, 0, bounce, slot, slot, slot, blen, bif, cnt);
             if (rc == 0 && hipStreamSynchronize(ctx->hstream[0]) != hipSuccess) rc = fail(-EIO, "retry chunk");
             for (size_t k = 0; rc == 0 && k < cnt; ++k) {
-                size_t j = idx[k];
+                size_t j = idx[HFV_MUT_HOSTCHUNK == 6 ? cnt - 1 - k : k];
                 memcpy(frames + j * slot, ctx->brh_hwin[0] + k * slot, slot);
                 action[j] = ctx->brh_hio[0][kBrChunk * 6 + k];
                 verdict[j] = ctx->brh_hio[0][kBrChunk * 7 + k];
@@ -502,14 +585,14 @@ int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_
     if (rc) return rc;
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
+    hc_reset();
     if (const uint8_t *drecs = host_dev_ptr(ctx, recs, (n - 1) * stride + ctx->hf_off + 12))
         return verify_records_zero_copy(ctx, drecs, stride, n, pass_bits);
     // Staging: each chunk's records are gathered on the host into a compact pinned layout of
     // kHostRec bytes per record (INF at 0, HF at 8: the 20 bytes the verifier reads), so
     // PCIe moves 24 B instead of the record stride; the gather is split over host threads
     // and chunk c's gather overlaps chunk c-1's copy, kernel and copy-back on the other stream.
-    const size_t chunk = (size_t)1 << 18;   // records per chunk
-    if (ctx->host_chunk < chunk * kHostRec) {
+    if (ctx->host_chunk < kRecChunk * kHostRec) {
         for (int i = 0; i < 2; ++i) {
             if (ctx->h_pin[i]) (void)hipHostFree(ctx->h_pin[i]);
             if (ctx->d_rec[i]) (void)hipFree(ctx->d_rec[i]);
@@ -518,14 +601,16 @@ int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_
             ctx->h_pin[i] = ctx->d_rec[i] = nullptr;
             ctx->h_bits[i] = ctx->d_bits[i] = nullptr;
             if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
-            HIP_TRY(hipHostMalloc((void **)&ctx->h_pin[i], chunk * kHostRec, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&ctx->d_rec[i], chunk * kHostRec));
-            HIP_TRY(hipHostMalloc((void **)&ctx->h_bits[i], chunk / 8, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&ctx->d_bits[i], chunk / 8));
+            HIP_TRY(hipHostMalloc((void **)&ctx->h_pin[i], kRecChunk * kHostRec, hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&ctx->d_rec[i], kRecChunk * kHostRec));
+            HIP_TRY(hipHostMalloc((void **)&ctx->h_bits[i], kRecChunk / 8, hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&ctx->d_bits[i], kRecChunk / 8));
         }
-        ctx->host_chunk = chunk * kHostRec;
+        ctx->host_chunk = kRecChunk * kHostRec;
     }
+    const size_t chunk = rec_chunk();   // records per chunk
     size_t nchunks = (n + chunk - 1) / chunk;
+    hc_add(kHcChunks, nchunks);
     size_t pending_words[2] = {0, 0};
     size_t pending_first[2] = {0, 0};
     for (size_t c = 0; c < nchunks + 2; ++c) {
@@ -533,18 +618,25 @@ int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_
         hipStream_t st = ctx->hstream[slot];
         if (c >= 2) {   // retire chunk c-2 (same slot)
             HIP_TRY(hipStreamSynchronize(st));
-            memcpy(pass_bits + pending_first[slot], ctx->h_bits[slot], pending_words[slot] * 8);
+            size_t to = pending_first[slot], words = pending_words[slot];
+            if (HFV_MUT_HOSTCHUNK == 1) {
+                to = pending_first[slot ^ 1];
+                if (words > (n + 63) / 64 - to) words = (n + 63) / 64 - to;
+            }
+            memcpy(pass_bits + to, ctx->h_bits[slot], words * 8);
         }
         if (c >= nchunks) continue;
+        if (c >= 2) hc_add(kHcReuses, 1);
         size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
-        gather_hf(ctx->h_pin[slot], (const uint8_t *)recs + first * stride, stride, ctx->inf_off, ctx->hf_off, cnt);
+        const size_t from = HFV_MUT_HOSTCHUNK == 3 ? first * kHostRec : first * stride;
+        gather_hf(ctx->h_pin[slot], (const uint8_t *)recs + from, stride, ctx->inf_off, ctx->hf_off, cnt);
         HIP_TRY(hipMemcpyAsync(ctx->d_rec[slot], ctx->h_pin[slot], cnt * kHostRec, hipMemcpyHostToDevice, st));
         rc = with_tables(ctx, st, "verify_records launch", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
             return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, ctx->d_rec[slot],
                                          kHostRec, cnt, 0, 8, ctx->d_bits[slot], st);
         });
         if (rc) return rc;
-        size_t words = (cnt + 63) / 64;
+        size_t words = HFV_MUT_HOSTCHUNK == 2 ? cnt / 64 : (cnt + 63) / 64;
         HIP_TRY(hipMemcpyAsync(ctx->h_bits[slot], ctx->d_bits[slot], words * 8, hipMemcpyDeviceToHost, st));
         pending_words[slot] = words;
         pending_first[slot] = first / 64;

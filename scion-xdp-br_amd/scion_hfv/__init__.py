@@ -22,7 +22,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv.so")
 # the test build: the same library plus the test hooks (hfv_debug_relay_delay, _publish_delay,
-# _br_grid, _br_split, _batch_grid, _loop_host_stage, _service_set_weights); loaded only by tests (HFV_LIB),
+# _br_grid, _br_split, _batch_grid, _loop_host_stage, _service_set_weights, the host paths' chunk hooks);
+# loaded only by tests (HFV_LIB),
 # never by the product path
 TEST_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv_test.so")
 
@@ -924,6 +925,30 @@ class Ctx:
     def debug_frames_host_chunk(frames):
         """Test-only: frames per chunk of verify_frames_host (a multiple of 64; 0 = the default)."""
         _check(lib().hfv_debug_frames_host_chunk(ctypes.c_size_t(frames)))
+
+    @staticmethod
+    def debug_records_host_chunk(records):
+        """Test-only: records per chunk of verify_records_host (a multiple of 64; 0 = the default)."""
+        _check(lib().hfv_debug_records_host_chunk(ctypes.c_size_t(records)))
+
+    @staticmethod
+    def debug_br_host_chunk(frames):
+        """Test-only: frames per chunk and per retry round of br_process_host (0 = the default)."""
+        _check(lib().hfv_debug_br_host_chunk(ctypes.c_size_t(frames)))
+
+    @staticmethod
+    def debug_host_inline_rows(rows):
+        """Test-only: the row count from which the host paths' staging copies go through the host
+        thread pool (0 = the default, 8192)."""
+        _check(lib().hfv_debug_host_inline_rows(ctypes.c_size_t(rows)))
+
+    @staticmethod
+    def debug_host_chunk_counts():
+        """Test-only, read-only: (chunks launched in the first pass, retry rounds, frames retried,
+        chunks that reused a stream slot) of the process's last verify_records_host / br_process_host."""
+        out = (ctypes.c_uint64 * 4)()
+        _check(lib().hfv_debug_host_chunk_counts(out))
+        return tuple(int(x) for x in out)
 
 
 # ---- full BR path (config 4): router tables --------------------------------------------------
