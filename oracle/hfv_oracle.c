@@ -322,6 +322,37 @@ void orc_verify_records_mt(const uint8_t *recs, size_t stride, size_t n,
     for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
 }
 
+typedef struct {
+    const uint8_t *mi, *kidx; size_t n0, n1;
+    const orc_hop_key *keys; const uint32_t *valid; uint8_t *tags;
+} tag_job;
+
+static void *tag_worker(void *p)
+{
+    tag_job *j = (tag_job *)p;
+    for (size_t i = j->n0; i < j->n1; ++i) {
+        uint32_t idx = j->kidx ? j->kidx[i] : 0;
+        if ((j->valid[idx >> 5] >> (idx & 31)) & 1) orc_cmac16(j->mi + 16 * i, &j->keys[idx], j->tags + 16 * i);
+        else memset(j->tags + 16 * i, 0, 16);
+    }
+    return NULL;
+}
+
+void orc_cmac16_bulk(const uint8_t *mi, const uint8_t *kidx, size_t n, const orc_hop_key *keys,
+                     const uint32_t valid[8], uint8_t *tags, int nthreads)
+{
+    if (nthreads < 1) nthreads = 1;
+    if (nthreads > 256) nthreads = 256;
+    pthread_t th[256];
+    tag_job jobs[256];
+    for (int t = 0; t < nthreads; ++t) {
+        jobs[t] = (tag_job){mi, kidx, n * (size_t)t / (size_t)nthreads, n * (size_t)(t + 1) / (size_t)nthreads,
+                            keys, valid, tags};
+        pthread_create(&th[t], NULL, tag_worker, &jobs[t]);
+    }
+    for (int t = 0; t < nthreads; ++t) pthread_join(th[t], NULL);
+}
+
 /* ---------------------------------------------------------------------------------- */
 /* Synthetic records                       */
 /* ---------------------------------------------------------------------------------- */

@@ -59,6 +59,11 @@ int orc_verify_hop_field(const uint8_t mi[16], uint64_t expected, const orc_hop_
 /* CMAC tag of one 16-byte block = aes_cmac_16bytes (aes.h:129-141) */
 void orc_cmac16(const uint8_t mi[16], const orc_hop_key *key, uint8_t tag[16]);
 
+/* orc_cmac16 over n macinputs, split over nthreads pthreads: tags[i] = the tag of mi[i] under
+ * keys[kidx[i]] (kidx NULL: slot 0), or 16 zero bytes where that slot's valid bit is clear. */
+void orc_cmac16_bulk(const uint8_t *mi, const uint8_t *kidx, size_t n, const orc_hop_key *keys,
+                     const uint32_t valid[8], uint8_t *tags, int nthreads);
+
 /* ---- 64 B synthetic SCION record batch -------------------- */
 enum { ORC_KEYSEL_ZERO = 0, ORC_KEYSEL_IFID = 1 };
 #define ORC_REC_INF_OFF 40

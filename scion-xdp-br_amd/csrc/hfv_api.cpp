@@ -72,6 +72,23 @@ LaunchGeom batch_geom(const hfv_ctx *ctx)
     g.batch_grid_cap = g_batch_grid;
     return g;
 }
+// hfv_debug_aux_grid: blocks per k_macinputs, k_count_verdicts and k_gen_records launch (0 = today's
+// grid; otherwise the smaller of that grid and `blocks`), for hfv_verify_macinputs, hfv_cmac_tags,
+// hfv_verdict_counters and hfv_gen_records.  With 1 to 3 blocks of 512 threads a round holds 512 to
+// 1536 items, so a few thousand items give every wave five rounds and more of its grid-stride loop --
+// what the real grid reaches only past a million (tests/test_gpu_aux_edges.py).
+static unsigned g_aux_grid = 0;
+extern "C" int hfv_debug_aux_grid(unsigned blocks)
+{
+    g_aux_grid = blocks;
+    return 0;
+}
+LaunchGeom aux_geom(const hfv_ctx *ctx)
+{
+    LaunchGeom g = ctx->geom;
+    g.aux_grid_cap = g_aux_grid;
+    return g;
+}
 #endif
 
 int check_records(const hfv_ctx *ctx, const void *recs, size_t stride, const void *bits)
@@ -317,7 +334,7 @@ int hfv_key_add_batch(hfv_ctx *ctx, uint32_t first, const struct aes_key *keys, 
     }
     int rc = 0;
     if (hipMemcpyAsync(d_raw, keys, 16 * n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = -EIO;
-    if (!rc && launch_expand_keys(d_raw, n, d_hk, nullptr, 0, ctx->stream) != 0) rc = -EIO;
+    if (!rc && launch_expand_keys(d_raw, n, d_hk, ctx->stream) != 0) rc = -EIO;
     hop_key *tmp = (hop_key *)malloc(sizeof(hop_key) * n);
     if (!tmp) rc = -ENOMEM;
     if (!rc && hipMemcpyAsync(tmp, d_hk, sizeof(hop_key) * n, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) rc = -EIO;
@@ -794,7 +811,7 @@ int hfv_verify_macinputs(hfv_ctx *ctx, const struct macinput *mi, const uint64_t
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
     return with_tables(ctx, (hipStream_t)stream, "verify_macinputs launch", [&](DevState *ds) {
-        return launch_verify_macinputs(ctx->geom, &ds->keys, mi, expected, key_index, n, pass_bits, stream);
+        return launch_verify_macinputs(aux_geom(ctx), &ds->keys, mi, expected, key_index, n, pass_bits, stream);
     });
 }
 
@@ -808,7 +825,7 @@ int hfv_cmac_tags(hfv_ctx *ctx, const struct macinput *mi, const uint8_t *key_in
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
     return with_tables(ctx, (hipStream_t)stream, "cmac_tags launch", [&](DevState *ds) {
-        return launch_cmac_tags(ctx->geom, &ds->keys, mi, key_index, n, tags, stream);
+        return launch_cmac_tags(aux_geom(ctx), &ds->keys, mi, key_index, n, tags, stream);
     });
 }
 
@@ -820,7 +837,7 @@ int hfv_expand_keys(hfv_ctx *ctx, const struct aes_key *keys, size_t n, struct h
     if (((uintptr_t)keys & 15) || ((uintptr_t)out & 15)) return fail(-EINVAL, "buffers must be 16-byte aligned");
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
-    int e = launch_expand_keys((const uint8_t *)keys, n, out, nullptr, 0, stream);
+    int e = launch_expand_keys((const uint8_t *)keys, n, out, stream);
     if (e != hipSuccess) return hip_fail((hipError_t)e, "expand_keys launch");
     return 0;
 }
@@ -838,7 +855,7 @@ int hfv_gen_records(hfv_ctx *ctx, void *recs, size_t stride, size_t n, uint64_t 
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
     return with_tables(ctx, (hipStream_t)stream, "gen_records launch", [&](DevState *ds) {
-        return launch_gen_records(ctx->geom, &ds->keys, ctx->keysel, (uint8_t *)recs, stride, n, seed, first_index,
+        return launch_gen_records(aux_geom(ctx), &ds->keys, ctx->keysel, (uint8_t *)recs, stride, n, seed, first_index,
                                   stream);
     });
 }
@@ -854,7 +871,7 @@ int hfv_verdict_counters(hfv_ctx *ctx, const void *recs, size_t stride, size_t n
     if ((uintptr_t)counters & 7) return fail(-EINVAL, "bitmap and counters must be 8-byte aligned");
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
-    int e = launch_count_verdicts(ctx->geom, (const uint8_t *)recs, stride, n, ctx->inf_off, ctx->hf_off, pass_bits,
+    int e = launch_count_verdicts(aux_geom(ctx), (const uint8_t *)recs, stride, n, ctx->inf_off, ctx->hf_off, pass_bits,
                                   counters, stream);
     if (e != hipSuccess) return hip_fail((hipError_t)e, "count_verdicts launch");
     return 0;

@@ -1,6 +1,21 @@
 // hfv_aux_kernels.hip -- gfx950 (MI355X) kernels beside the hop-field verify paths: prepared
 // macinputs (verify or full tags), key expansion, the synthetic record generator, the verdict
 // counters and the diagnostic streaming read, with their launchers.
+//
+// HFV_MUT_AUX=N (make auxedge; 0: the product): one deliberately wrong step in one of these kernels,
+// which tests/test_gpu_aux_edges.py must fail on.  Every mutant picks a wrong index inside the array the
+// right one lies in, or drops a condition: none changes a loop's start, step or bound, and none reads or
+// writes outside the arrays the product touches.
+//   1  k_macinputs (verify) writes the verdict word of every round after a wave's first to the first
+//      round's word index
+//   2  k_macinputs (tags) does not zero the tag of an invalid key slot
+//   3  k_macinputs (verify) masks `expected` to 48 bits as well: bits 48..63 of it are ignored
+//   4  k_count_verdicts takes the pass bit from the word of the thread's first round
+//   5  k_gen_records forms the draw index 4 * i in 32 bits
+//   6  k_gen_records writes row j at j * 64 instead of j * stride
+#ifndef HFV_MUT_AUX
+#define HFV_MUT_AUX 0
+#endif
 #include <hip/hip_runtime.h>
 
 #include <hip/hip_ext.h>
@@ -67,16 +82,26 @@ __global__ __launch_bounds__(BLOCK) void k_macinputs(const DevKeyTable *__restri
         if constexpr (MODE == kModeTags) {
             uint32_t o[4];
             round_last_full<2>(s, key.row(10), l, o);
+#if HFV_MUT_AUX != 2
             if (!key.ok()) o[0] = o[1] = o[2] = o[3] = 0;
+#endif
             if (in) tags[i] = make_uint4(o[0], o[1], o[2], o[3]);
         } else {
             uint32_t t0, t1;
             round_last_48<2>(s, key.row(10), l, t0, t1);
             uint2 e = in ? expected[i] : make_uint2(0, 0);
             // actual = tag bytes 0..5 as LE u64 (upper 16 bits zero) == expected (xdp.c:89-90)
+#if HFV_MUT_AUX == 3
+            bool pass = in && key.ok() && t0 == e.x && (t1 & 0xffffu) == (e.y & 0xffffu);
+#else
             bool pass = in && key.ok() && t0 == e.x && (t1 & 0xffffu) == e.y;
+#endif
             uint64_t ballot = __ballot(pass);
+#if HFV_MUT_AUX == 1
+            if (lane == 0) bits[t < nwaves ? t : wave] = ballot;
+#else
             if (lane == 0) bits[t] = ballot;
+#endif
         }
     }
 }
@@ -97,8 +122,7 @@ __device__ __forceinline__ uint32_t tg(int row, uint32_t x)
 __device__ __forceinline__ uint32_t bswap(uint32_t x) { return __builtin_bswap32(x); }
 
 __global__ __launch_bounds__(256) void k_expand_keys(const uint4 *__restrict__ raw, uint64_t n,
-                                                     hop_key *__restrict__ out, DevKeyTable *__restrict__ tab,
-                                                     uint32_t first_slot)
+                                                     hop_key *__restrict__ out)
 {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -138,31 +162,10 @@ __global__ __launch_bounds__(256) void k_expand_keys(const uint4 *__restrict__ r
     q2 = (q2 << 1) | (q3 >> 31);
     q3 = (q3 << 1) ^ (msb ? 0x87u : 0u);
     uint32_t k1[4] = {bswap(q0), bswap(q1), bswap(q2), bswap(q3)};
-    if (out) {
-        uint4 *o = reinterpret_cast<uint4 *>(out + i);
+    uint4 *o = reinterpret_cast<uint4 *>(out + i);
 #pragma unroll
-        for (int r = 0; r < 11; ++r) o[r] = make_uint4(w[4 * r], w[4 * r + 1], w[4 * r + 2], w[4 * r + 3]);
-        o[11] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
-    }
-    if (tab) {   // compiled device image (hfv_tables.h), same as compile_dev_key on the host
-        uint32_t slot = first_slot + (uint32_t)i;
-        uint32_t k0[4] = {w[0] ^ k1[0], w[1] ^ k1[1], w[2] ^ k1[2], w[3] ^ k1[3]};
-        uint32_t *row0 = tab->rows[0][slot];
-        row0[0] = k0[0]; row0[1] = k0[1]; row0[2] = k0[2]; row0[3] = k0[3];
-        for (int r = 1; r < 11; ++r) {   // rows 1..9 pre-rotated by 16 (hfv_tables.h)
-            uint32_t *p = tab->rows[r][slot];
-            int rot = r < 10 ? 16 : 0;
-            for (int c = 0; c < 4; ++c) p[c] = rot ? __builtin_amdgcn_alignbit(w[4 * r + c], w[4 * r + c], 16) : w[4 * r + c];
-        }
-        uint32_t *p = tab->rows[11][slot];
-        p[0] = w[4] ^ tg(0, k0[0]) ^ tg(3, k0[3] >> 24);
-        p[1] = w[5] ^ tg(2, k0[3] >> 16);
-        p[2] = w[6] ^ tg(0, k0[2]);
-        p[3] = w[7] ^ tg(1, k0[0] >> 8);
-        for (int r = 3; r <= 10; ++r)   // schedule words t_r = w[4r] ^ w[4r-4] (hfv_internal.h)
-            tab->sched[(r - 3) >> 2][slot][(r - 3) & 3] = w[4 * r] ^ w[4 * r - 4];
-        atomicOr(&tab->valid[slot >> 5], 1u << (slot & 31));
-    }
+    for (int r = 0; r < 11; ++r) o[r] = make_uint4(w[4 * r], w[4 * r + 1], w[4 * r + 2], w[4 * r + 3]);
+    o[11] = make_uint4(k1[0], k1[1], k1[2], k1[3]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -188,8 +191,13 @@ __global__ __launch_bounds__(BLOCK) void k_gen_records(const DevKeyTable *__rest
     const Lane l = lane_bases();
     for (uint64_t j = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; j < n; j += (uint64_t)gridDim.x * BLOCK) {
         uint64_t i = first_index + j;
-        uint64_t r0 = splitmix_at(seed, 4 * i), r1 = splitmix_at(seed, 4 * i + 1);
-        uint64_t r2 = splitmix_at(seed, 4 * i + 2), r3 = splitmix_at(seed, 4 * i + 3);
+#if HFV_MUT_AUX == 5
+        const uint64_t k = (uint32_t)(4 * i);
+#else
+        const uint64_t k = 4 * i;
+#endif
+        uint64_t r0 = splitmix_at(seed, k), r1 = splitmix_at(seed, k + 1);
+        uint64_t r2 = splitmix_at(seed, k + 2), r3 = splitmix_at(seed, k + 3);
         uint32_t cons = (uint32_t)r0 & 1u;
         uint32_t beta = (uint32_t)(r0 >> 8) & 0xffffu;
         uint32_t ts_w = bswap((uint32_t)(r0 >> 32));
@@ -210,7 +218,11 @@ __global__ __launch_bounds__(BLOCK) void k_gen_records(const DevKeyTable *__rest
         uint4 q1 = make_uint4(0x10000000u, 0x00ff0100u, 0x11000000u, 0x0100000au);
         uint4 q2 = make_uint4(0x0200000au, 0x00100000u, cons | (bswap16(seg) << 16), ts_w);
         uint4 q3 = make_uint4(hf0, hf1 | ((uint32_t)mac << 16), (uint32_t)(mac >> 16), bswap((uint32_t)i));
+#if HFV_MUT_AUX == 6
+        uint4 *o = reinterpret_cast<uint4 *>(recs + j * 64);
+#else
         uint4 *o = reinterpret_cast<uint4 *>(recs + j * stride);
+#endif
         o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
     }
 }
@@ -220,10 +232,16 @@ __global__ __launch_bounds__(BLOCK) void k_gen_records(const DevKeyTable *__rest
 // ---------------------------------------------------------------------------------------
 constexpr int kBlockAux = 512;
 
+// the test build's hfv_debug_aux_grid (g.aux_grid_cap; always 0 in the product library)
+static inline unsigned aux_capped(const LaunchGeom &g, unsigned grid)
+{
+    return g.aux_grid_cap && g.aux_grid_cap < grid ? g.aux_grid_cap : grid;
+}
+
 int launch_verify_macinputs(const LaunchGeom &g, const DevKeyTable *tab, const void *mi, const uint64_t *expected,
                             const uint8_t *kidx, size_t n, uint64_t *bits, void *stream)
 {
-    unsigned grid = grid_for(n, kBlockAux, g.num_cus, 2);
+    unsigned grid = aux_capped(g, grid_for(n, kBlockAux, g.num_cus, 2));
     hipLaunchKernelGGL((k_macinputs<kModeMacinputs, kBlockAux>), dim3(grid), dim3(kBlockAux), 0, (hipStream_t)stream,
                        tab, (const uint4 *)mi, (const uint2 *)expected, kidx, (uint64_t)n, bits, (uint4 *)nullptr);
     return (int)hipGetLastError();
@@ -232,19 +250,18 @@ int launch_verify_macinputs(const LaunchGeom &g, const DevKeyTable *tab, const v
 int launch_cmac_tags(const LaunchGeom &g, const DevKeyTable *tab, const void *mi, const uint8_t *kidx, size_t n,
                      void *tags, void *stream)
 {
-    unsigned grid = grid_for(n, kBlockAux, g.num_cus, 2);
+    unsigned grid = aux_capped(g, grid_for(n, kBlockAux, g.num_cus, 2));
     hipLaunchKernelGGL((k_macinputs<kModeTags, kBlockAux>), dim3(grid), dim3(kBlockAux), 0, (hipStream_t)stream, tab,
                        (const uint4 *)mi, (const uint2 *)nullptr, kidx, (uint64_t)n, (uint64_t *)nullptr,
                        (uint4 *)tags);
     return (int)hipGetLastError();
 }
 
-int launch_expand_keys(const uint8_t *raw, size_t n, hop_key *out, DevKeyTable *tab, uint32_t first_slot,
-                       void *stream)
+int launch_expand_keys(const uint8_t *raw, size_t n, hop_key *out, void *stream)
 {
     unsigned grid = (unsigned)((n + 255) / 256);
     hipLaunchKernelGGL(k_expand_keys, dim3(grid ? grid : 1), dim3(256), 0, (hipStream_t)stream, (const uint4 *)raw,
-                       (uint64_t)n, out, tab, first_slot);
+                       (uint64_t)n, out);
     return (int)hipGetLastError();
 }
 
@@ -268,7 +285,12 @@ __global__ __launch_bounds__(kCountBlock) void k_count_verdicts(const uint8_t *_
         const uint8_t *r = recs + i * stride;
         // Cons ? ConsIngress : ConsEgress, low byte of the big-endian field (rec_key_slot)
         const uint32_t slot = (r[inf_off] & 1u) ? r[hf_off + 3] : r[hf_off + 5];
+#if HFV_MUT_AUX == 4
+        const uint64_t first = (uint64_t)blockIdx.x * kCountBlock + threadIdx.x;
+        const uint32_t pass = (uint32_t)(bits[first >> 6] >> (i & 63)) & 1u;
+#else
         const uint32_t pass = (uint32_t)(bits[i >> 6] >> (i & 63)) & 1u;
+#endif
         atomicAdd(&h[slot * 2 + (pass ^ 1u)], 1u);
     }
     __syncthreads();
@@ -279,7 +301,7 @@ __global__ __launch_bounds__(kCountBlock) void k_count_verdicts(const uint8_t *_
 int launch_count_verdicts(const LaunchGeom &g, const uint8_t *recs, size_t stride, size_t n, uint32_t inf_off,
                           uint32_t hf_off, const uint64_t *bits, uint64_t *counters, void *stream)
 {
-    unsigned grid = grid_for(n, kCountBlock, g.num_cus, 1);
+    unsigned grid = aux_capped(g, grid_for(n, kCountBlock, g.num_cus, 1));
     hipLaunchKernelGGL(k_count_verdicts, dim3(grid), dim3(kCountBlock), 0, (hipStream_t)stream, recs, (uint64_t)stride,
                        (uint64_t)n, inf_off, hf_off, bits, (unsigned long long *)counters);
     return (int)hipGetLastError();
@@ -290,7 +312,7 @@ int launch_gen_records(const LaunchGeom &g, const DevKeyTable *tab, int keysel, 
 {
     uint64_t blocks = (n + kBlockAux - 1) / kBlockAux;
     uint64_t cap = (uint64_t)g.num_cus * 2;
-    unsigned grid = (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap);
+    unsigned grid = aux_capped(g, (unsigned)(blocks < cap ? (blocks ? blocks : 1) : cap));
     hipLaunchKernelGGL((k_gen_records<kBlockAux>), dim3(grid), dim3(kBlockAux), 0, (hipStream_t)stream, tab, keysel,
                        recs, (uint64_t)stride, (uint64_t)n, seed, first_index);
     return (int)hipGetLastError();

@@ -174,13 +174,16 @@ int after_launch(hfv_ctx *ctx, hipStream_t st, int err, const char *what, bool r
 int check_records(const hfv_ctx *ctx, const void *recs, size_t stride, const void *bits);
 // The router kernel's launch geometry: the ctx's, with the test build's hfv_debug_br_grid / br_split.
 // The batch-list launch's (launch_verify_batches, also behind launch_verify_records): the ctx's, with
-// the test build's hfv_debug_batch_grid.
+// the test build's hfv_debug_batch_grid.  The macinput, tag, verdict-counter and generator launches'
+// (hfv_aux_kernels.hip): the ctx's, with the test build's hfv_debug_aux_grid.
 #ifdef HFV_TEST_HOOKS
 LaunchGeom br_geom(const hfv_ctx *ctx);
 LaunchGeom batch_geom(const hfv_ctx *ctx);
+LaunchGeom aux_geom(const hfv_ctx *ctx);
 #else
 #define br_geom(ctx) ((ctx)->geom)
 #define batch_geom(ctx) ((ctx)->geom)
+#define aux_geom(ctx) ((ctx)->geom)
 #endif
 
 #pragma GCC visibility pop

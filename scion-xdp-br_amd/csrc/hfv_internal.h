@@ -176,6 +176,9 @@ struct LaunchGeom {
     uint64_t br_split_cap = 0;
     // the same for the batch-list launch (hfv_debug_batch_grid): blocks per k_verify_batches launch
     unsigned batch_grid_cap = 0;
+    // and for the macinput, tag, verdict-counter and generator launches (hfv_debug_aux_grid): blocks
+    // per k_macinputs / k_count_verdicts / k_gen_records launch
+    unsigned aux_grid_cap = 0;
 };
 
 // kernel launchers; return hipError_t as int.  Record and batch-list verify, key_prologue:
@@ -205,8 +208,7 @@ int launch_verify_macinputs(const LaunchGeom &g, const DevKeyTable *tab, const v
                             const uint8_t *kidx, size_t n, uint64_t *bits, void *stream);
 int launch_cmac_tags(const LaunchGeom &g, const DevKeyTable *tab, const void *mi, const uint8_t *kidx, size_t n,
                      void *tags, void *stream);
-int launch_expand_keys(const uint8_t *raw, size_t n, hop_key *out, DevKeyTable *tab, uint32_t first_slot,
-                       void *stream);
+int launch_expand_keys(const uint8_t *raw, size_t n, hop_key *out, void *stream);
 int launch_count_verdicts(const LaunchGeom &g, const uint8_t *recs, size_t stride, size_t n, uint32_t inf_off,
                           uint32_t hf_off, const uint64_t *bits, uint64_t *counters, void *stream);
 int launch_gen_records(const LaunchGeom &g, const DevKeyTable *tab, int keysel, uint8_t *recs, size_t stride,

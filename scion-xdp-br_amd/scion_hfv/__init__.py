@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv.so")
 # the test build: the same library plus the test hooks (hfv_debug_relay_delay, _publish_delay,
-# _br_grid, _br_split, _batch_grid, _loop_host_stage, _service_set_weights, the host paths' chunk hooks);
+# _br_grid, _br_split, _batch_grid, _aux_grid, _loop_host_stage, _service_set_weights, the host paths' chunk hooks);
 # loaded only by tests (HFV_LIB),
 # never by the product path
 TEST_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv_test.so")
@@ -681,6 +681,12 @@ class Ctx:
         and k_verify_frames / k_verify_frames_list launches (verify_frames_fused, verify_frames_batches)
         at `blocks` blocks (0 = default geometry)."""
         _check(lib().hfv_debug_batch_grid(ctypes.c_uint(blocks)))
+
+    @staticmethod
+    def debug_aux_grid(blocks):
+        """Test-only: cap k_macinputs (verify_macinputs, cmac_tags), k_count_verdicts (verdict_counters)
+        and k_gen_records (gen_records) launches at `blocks` blocks (0 = default geometry)."""
+        _check(lib().hfv_debug_aux_grid(ctypes.c_uint(blocks)))
 
     @staticmethod
     def debug_br_split(frames):

@@ -105,6 +105,18 @@ def verify_records(recs, hop_keys, valid, keysel, stride=64, n=None, nthreads=1)
     return bits
 
 
+def cmac16_bulk(mi, hop_keys, valid, key_index=None, nthreads=8):
+    """Full 16-byte tags of macinput[n, 16] under hop_keys[key_index[i]] (slot 0 without an index);
+    16 zero bytes where the slot is not valid (orc_cmac16_bulk)."""
+    mi = np.ascontiguousarray(mi, dtype=np.uint8)
+    n = len(mi)
+    tags = np.zeros((n, 16), dtype=np.uint8)
+    kidx = None if key_index is None else np.ascontiguousarray(key_index, dtype=np.uint8)
+    oracle().orc_cmac16_bulk(_vp(mi), None if kidx is None else _vp(kidx), ctypes.c_size_t(n), _vp(hop_keys),
+                             _vp(np.ascontiguousarray(valid, dtype=np.uint32)), _vp(tags), ctypes.c_int(nthreads))
+    return tags
+
+
 def ref_verify_records(recs, raw_keys_256: bytes, hop_keys, valid, keysel, nthreads=1, aesni=0, stride=64, n=None):
     """Reference aes.c (soft) or AES-NI path over the same records; None if not built."""
     R = reference()
