@@ -182,23 +182,11 @@ int hfv_ctx_destroy(hfv_ctx *ctx)
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     for (int i = 0; i < 2; ++i) {
         if (ctx->hstream[i]) { (void)hipStreamSynchronize(ctx->hstream[i]); (void)hipStreamDestroy(ctx->hstream[i]); }
-        if (ctx->h_pin[i]) (void)hipHostFree(ctx->h_pin[i]);
-        if (ctx->h_bits[i]) (void)hipHostFree(ctx->h_bits[i]);
-        if (ctx->d_rec[i]) (void)hipFree(ctx->d_rec[i]);
-        if (ctx->d_bits[i]) (void)hipFree(ctx->d_bits[i]);
+        ctx->stage_in[i].release();
+        ctx->stage_out[i].release();
         for (int r = 0; r < 8; ++r)
             if (ctx->reader_ev[i][r]) (void)hipEventDestroy(ctx->reader_ev[i][r]);
         if (ctx->dev_tab[i]) (void)hipFree(ctx->dev_tab[i]);
-    }
-    for (int i = 0; i < 2; ++i) {
-        if (ctx->brh_dwin[i]) (void)hipFree(ctx->brh_dwin[i]);
-        if (ctx->brh_hwin[i]) (void)hipHostFree(ctx->brh_hwin[i]);
-        if (ctx->brh_dio[i]) (void)hipFree(ctx->brh_dio[i]);
-        if (ctx->brh_hio[i]) (void)hipHostFree(ctx->brh_hio[i]);
-        if (ctx->fh_din[i]) (void)hipFree(ctx->fh_din[i]);
-        if (ctx->fh_hin[i]) (void)hipHostFree(ctx->fh_hin[i]);
-        if (ctx->fh_dout[i]) (void)hipFree(ctx->fh_dout[i]);
-        if (ctx->fh_hout[i]) (void)hipHostFree(ctx->fh_hout[i]);
     }
     if (ctx->brh_dstats) (void)hipFree(ctx->brh_dstats);
     if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
@@ -598,17 +586,7 @@ static int verify_frames_fused(hfv_ctx *ctx, const uint8_t *frames, size_t slot,
     SVC_QUIESCE(ctx);
     const bool reader = launch_reads_tables(ctx->keysel);
     return with_tables(ctx, (hipStream_t)stream, "verify_frames_fused launch", reader, [&](DevState *ds) {
-        FusedArgs a;
-        memset(&a, 0, sizeof a);
-        a.frames = frames;
-        a.slot = slot;
-        a.lens = len;
-        a.ifindex = ingress_ifindex;
-        a.n = n;
-        a.status = status;
-        a.bits = (unsigned long long *)pass_bits;
-        a.tab = &ds->keys;
-        a.set = ctx->rx_set;
+        const FusedArgs a = fused_args(ctx, ds, frames, slot, len, ingress_ifindex, n, status, pass_bits);
         return launch_verify_frames(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, stream, ev0, ev1);
     });
 }

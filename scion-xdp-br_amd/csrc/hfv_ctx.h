@@ -41,6 +41,30 @@ struct DeviceGuard {
     }
 };
 
+// A pinned host buffer and its device twin of `cap` bytes: one stream slot's staging of the chunked
+// host paths.  reserve grows only; a failure leaves null pointers beside a zero cap.
+struct __attribute__((visibility("hidden"))) StagePair {
+    uint8_t *host = nullptr, *dev = nullptr;
+    size_t cap = 0;
+    int reserve(size_t bytes)
+    {
+        if (bytes <= cap) return 0;
+        release();
+        hipError_t e = hipMalloc((void **)&dev, bytes);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&host, bytes, hipHostMallocDefault);
+        if (e != hipSuccess) release();
+        cap = e == hipSuccess ? bytes : 0;
+        return e == hipSuccess ? 0 : hip_fail(e, "host-path staging");
+    }
+    void release()
+    {
+        if (dev) (void)hipFree(dev);
+        if (host) (void)hipHostFree(host);
+        host = dev = nullptr;
+        cap = 0;
+    }
+};
+
 }  // namespace hfv
 
 using namespace hfv;   // every unit that includes this header is library code
@@ -66,13 +90,14 @@ struct hfv_ctx {
     int nreaders[2] = {0, 0};
     bool readers_overflow[2] = {false, false};
     int active = 0;
-    // host-batch staging (hfv_verify_records_host)
+    // The chunked host paths (hfv_verify_records_host, hfv_br_process_host, hfv_verify_frames_host):
+    // two streams and each one's staging, what a chunk copies up and what it copies back.  The three
+    // calls share it: none runs beside another on a ctx, and each waits for both streams before its
+    // first chunk.  Records: in = the 24-byte compact records, out = the bitmap words.  Router: in =
+    // the packed header windows (both ways), out = len u16 | ifindex u32 | action u8 | verdict u8 |
+    // egress i32, each at its kBrChunk offset.  Frames: in and out as FhLayout says.
     hipStream_t hstream[2] = {nullptr, nullptr};
-    uint8_t *h_pin[2] = {nullptr, nullptr};
-    uint8_t *d_rec[2] = {nullptr, nullptr};
-    uint64_t *h_bits[2] = {nullptr, nullptr};
-    uint64_t *d_bits[2] = {nullptr, nullptr};
-    size_t host_chunk = 0;
+    StagePair stage_in[2], stage_out[2];
     // attached pinned key map
     const void *keymap = nullptr;
     uint32_t keymap_seq = 0xffffffffu;
@@ -88,21 +113,7 @@ struct hfv_ctx {
     // router tables for hfv_br_process (published with the key table)
     DevBrConfig br{};
     hfv_br_config cfg_src{};   // the tables as installed (checked against the build options)
-    // windowed host path (hfv_br_process_host): per-stream device/pinned chunk buffers
-    size_t brh_win_cap = 0;               // bytes per frame the device windows hold
-    uint8_t *brh_dwin[2] = {nullptr, nullptr};
-    uint8_t *brh_dio[2] = {nullptr, nullptr};   // len u16 | ifindex u32 | action u8 | verdict u8 | egress i32
-    uint8_t *brh_hio[2] = {nullptr, nullptr};   // pinned twin of brh_dio
-    uint8_t *brh_hwin[2] = {nullptr, nullptr};  // pinned twin of brh_dwin (packed header windows)
-    uint64_t *brh_dstats = nullptr;
-    // frames in host memory (hfv_verify_frames_host): per-stream chunk buffers, pinned and device.
-    // in: len u16[cnt] | ifindex u32[cnt] | packed windows (one H2D copy); out: verdict words |
-    // retry words | status u8[cnt] (one D2H copy).  Grown only when the window grows.
-    size_t fh_win_cap = 0;                      // bytes per frame the in buffers hold
-    uint8_t *fh_hin[2] = {nullptr, nullptr};
-    uint8_t *fh_din[2] = {nullptr, nullptr};
-    uint8_t *fh_hout[2] = {nullptr, nullptr};
-    uint8_t *fh_dout[2] = {nullptr, nullptr};
+    uint64_t *brh_dstats = nullptr;   // device verdict counters of one hfv_br_process_host call
     // host buffers registered with hfv_host_register (mapped: the kernels can address them)
     struct HostRange {
         uint8_t *host;
@@ -221,4 +232,22 @@ template <class Launch>
 static inline int with_tables(hfv_ctx *ctx, hipStream_t st, const char *what, Launch launch)
 {
     return with_tables(ctx, st, what, true, launch);
+}
+
+// What a caller fills of a frames-to-verdict-bits launch's argument (the launcher fills the key rows).
+static inline FusedArgs fused_args(const hfv_ctx *ctx, const DevState *ds, const uint8_t *frames, size_t slot,
+                                   const uint16_t *len, const uint32_t *ifx, size_t n, uint8_t *status, uint64_t *bits)
+{
+    FusedArgs a;
+    memset(&a, 0, sizeof a);
+    a.frames = frames;
+    a.slot = slot;
+    a.lens = len;
+    a.ifindex = ifx;
+    a.n = n;
+    a.status = status;
+    a.bits = (unsigned long long *)bits;
+    a.tab = &ds->keys;
+    a.set = ctx->rx_set;
+    return a;
 }

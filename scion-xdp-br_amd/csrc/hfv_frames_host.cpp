@@ -1,6 +1,8 @@
 // hfv_frames_host.cpp -- hfv_frame_locate and hfv_frame_extract: the frame parser
 // (hfv_frame_parse.h) over one frame in host memory, the scalar counterparts of the extract
-// kernels as hfv_verify_macinput is of the verify kernels.  No HIP dependency.
+// kernels as hfv_verify_macinput is of the verify kernels.  No HIP dependency.  Despite the name,
+// hfv_verify_frames_host (frames in host memory through the GPU) is not here: it is one of the
+// chunked host paths of hfv_host_path.cpp.
 #include <errno.h>
 #include <string.h>
 

@@ -1,50 +1,44 @@
 // hfv_host_path.cpp -- the entry points that take frames or records in host memory
-// (hfv_br_process_host, hfv_verify_records_host, hfv_verify_frames_host, hfv_host_register), their
-// staging workers (host thread pool, NUMA pinning), and the router stage of in-library pipelines
-// (hfv_loop.cpp).
+// (hfv_br_process_host, hfv_verify_records_host, hfv_verify_frames_host, hfv_host_register), what
+// their staging workers need of the machine (thread count, NUMA pinning), and the router stage of
+// in-library pipelines (hfv_loop.cpp).  The three chunked calls run on the two-slot schedule and the
+// worker pool of hfv_host_pipe.h and share the ctx's one staging set (host_stage).
 #include <pthread.h>
 #include <stdlib.h>
 
-#include <condition_variable>
-#include <functional>
-#include <mutex>
-#include <thread>
-
 #include "hfv_ctx.h"
+#include "hfv_host_pipe.h"
 
 // Compact staging record of the host path: INF (8 B) at 0, HF (12 B) at 8, 4 B pad.
 static constexpr size_t kHostRec = 24;
 
 // Records per chunk of hfv_verify_records_host (a multiple of 64, so that no bitmap word straddles two
 // chunks), frames per chunk and per retry round of hfv_br_process_host, and the row count below which
-// parallel_rows runs inline.  kBrChunk is also the layout constant of brh_dio / brh_hio / brh_dwin.
+// host_rows runs inline.  kBrChunk is also the layout constant of the router's stage_out.
 static const size_t kRecChunk = (size_t)1 << 18;
 static const size_t kBrChunk = (size_t)1 << 16;
 static const size_t kInlineRows = 8192;
 
 // HFV_MUT_HOSTCHUNK (make hostchunk; 0 in every product build): one deliberately wrong step of the
-// chunk pipelines below, each in bounds of every buffer and with every synchronisation kept:
-//   1  records: a retired chunk's bitmap is copied to the other slot's pending_first (cut at the end
-//      of the caller's bitmap)
+// chunk pipelines, each in bounds of every buffer and with every synchronisation kept:
+//   1  all three paths (two_slot_chunks, hfv_host_pipe.h): a retired chunk's results go to the place of
+//      the chunk on the other slot (cut at item n)
 //   2  records: a ragged chunk copies back cnt / 64 words (floor)
 //   3  records: chunks after the first gather from recs + first * kHostRec instead of first * stride
 //      (in bounds for stride >= kHostRec)
-//   4  router: a retired chunk's results go to first_of[sl ^ 1] (cut at frame n)
 //   5  router: the verdict counters are zeroed before every chunk instead of once per call (after the
 //      other stream has drained, so that the loss is the same in every run)
 //   6  router: a retry round's results are scattered through idx[cnt - 1 - k]
-// tests/test_gpu_host_chunks.py must fail on every one.
-#ifndef HFV_MUT_HOSTCHUNK
-#define HFV_MUT_HOSTCHUNK 0
-#endif
+// (4 was 1 in the router's own copy of the loop.)  tests/test_gpu_host_chunks.py must fail on every one,
+// tests/test_gpu_frames_hostmem.py on 1.
 
 #ifdef HFV_TEST_HOOKS
 // hfv_debug_records_host_chunk / _br_host_chunk / _host_inline_rows: the three counts above made small,
 // so that a few hundred records or frames span several chunks, reuse both stream slots, fill several
 // retry rounds and go through the host pool's partition; 0 restores the default.  The staging buffers
-// keep their full size: only the counts change.  hfv_debug_host_chunk_counts: what the last
-// hfv_verify_records_host / hfv_br_process_host call of the process ran (read-only): chunks launched in
-// the first pass, retry rounds, frames retried, chunks that reused a slot within the call.
+// keep their full size: only the counts change.  hfv_debug_host_chunk_counts: what the last host-path
+// call of the process ran (read-only): chunks launched in the first pass, retry rounds (second-run
+// chunks of hfv_verify_frames_host), frames retried, chunks that reused a slot within the call.
 static size_t g_rec_chunk = 0, g_br_chunk = 0, g_inline_rows = 0;
 static uint64_t g_hc_counts[4] = {0, 0, 0, 0};
 extern "C" int hfv_debug_records_host_chunk(size_t records)
@@ -162,97 +156,23 @@ void note_numa(int device)
     }
 }
 
-// Persistent host worker threads for the staging copies (spawning threads per copy cost more
-// than the copies: 32 spawns per 2^20-frame router batch).  Part 0 of every job runs on the
-// calling thread, parts 1..nt-1 on the workers.  Jobs come from one ctx thread at a time.
-class HostPool {
-  public:
-    explicit HostPool(int nt) : nt_(nt)
-    {
-        for (int k = 1; k < nt_; ++k) th_.emplace_back([this, k] {
-            pin_to_numa();
-            work(k);
-        });
-    }
-    ~HostPool()
-    {
-        {
-            std::lock_guard<std::mutex> g(m_);
-            stop_ = true;
-        }
-        cv_.notify_all();
-        for (auto &t : th_) t.join();
-    }
-    void run(size_t n, const std::function<void(size_t, size_t)> &fn)
-    {
-        std::unique_lock<std::mutex> lk(job_m_);   // one job at a time
-        {
-            std::lock_guard<std::mutex> g(m_);
-            fn_ = &fn;
-            n_ = n;
-            left_ = nt_ - 1;
-            ++gen_;
-        }
-        cv_.notify_all();
-        fn(0, n / nt_);
-        std::unique_lock<std::mutex> g(m_);
-        done_.wait(g, [this] { return left_ == 0; });
-        fn_ = nullptr;
-    }
-    int threads() const { return nt_; }
-
-  private:
-    void work(int k)
-    {
-        uint64_t seen = 0;
-        for (;;) {
-            const std::function<void(size_t, size_t)> *fn;
-            size_t n;
-            {
-                std::unique_lock<std::mutex> g(m_);
-                cv_.wait(g, [&] { return stop_ || gen_ != seen; });
-                if (stop_) return;
-                seen = gen_;
-                fn = fn_;
-                n = n_;
-            }
-            (*fn)(n * k / nt_, n * (k + 1) / nt_);
-            std::lock_guard<std::mutex> g(m_);
-            if (--left_ == 0) done_.notify_one();
-        }
-    }
-    int nt_;
-    std::vector<std::thread> th_;
-    std::mutex m_, job_m_;
-    std::condition_variable cv_, done_;
-    const std::function<void(size_t, size_t)> *fn_ = nullptr;
-    size_t n_ = 0;
-    int left_ = 0;
-    uint64_t gen_ = 0;
-    bool stop_ = false;
-};
-
 static HostPool &host_pool()
 {
-    static HostPool pool(host_threads());
+    static HostPool pool(host_threads(), pin_to_numa);
     return pool;
 }
 
 // fn(a, b) over [0, n) split into host_threads() contiguous parts (inline below kInlineRows items).
 template <class F>
-static void parallel_rows(size_t n, F fn)
+static void host_rows(size_t n, F fn)
 {
-    if (host_threads() <= 1 || n < inline_rows()) {
-        fn((size_t)0, n);
-        return;
-    }
-    host_pool().run(n, std::function<void(size_t, size_t)>(fn));
+    parallel_rows(host_threads(), inline_rows(), host_pool, n, fn);
 }
 
 // dst[i] = {INF, HF} of src record i (the verifier's 20 bytes).
 static void gather_hf(uint8_t *dst, const uint8_t *src, size_t stride, uint32_t inf_off, uint32_t hf_off, size_t n)
 {
-    parallel_rows(n, [=](size_t a, size_t b) {
+    host_rows(n, [=](size_t a, size_t b) {
         for (size_t i = a; i < b; ++i) {
             const uint8_t *r = src + i * stride;
             uint8_t *d = dst + i * kHostRec;
@@ -265,15 +185,11 @@ static void gather_hf(uint8_t *dst, const uint8_t *src, size_t stride, uint32_t 
 // Row copies between frames in their slots and packed windows: dst row i <- src row i.
 static void copy_rows(uint8_t *dst, size_t dpitch, const uint8_t *src, size_t spitch, size_t width, size_t n)
 {
-    parallel_rows(n, [=](size_t a, size_t b) {
+    host_rows(n, [=](size_t a, size_t b) {
         for (size_t i = a; i < b; ++i) memcpy(dst + i * dpitch, src + i * spitch, width);
     });
 }
 
-// Windowed host path.  Per chunk of br_chunk() frames, on alternating streams: strided H2D of
-// the windows + metadata, the kernel (stride = window, lengths clamped to the caller's slot),
-// strided D2H of the rewritten windows + results.  Then frames marked HFV_BR_ACTION_RETRY
-// (headers beyond the window) go through again with whole slots.
 static const size_t kBrStatWords = HFV_BR_STATS_IFINDEX * 2 * HFV_BR_COUNTERS;
 
 // The device verdict counters of one host-path call: allocated on first use, zeroed on `st`.
@@ -294,26 +210,35 @@ static int brh_add_stats(hfv_ctx *ctx, uint64_t *stats)
     return 0;
 }
 
-static int brh_buffers(hfv_ctx *ctx, size_t window)
+// The staging of one chunked call: both host streams exist and are idle (an earlier call that
+// returned an error midway may have left work on them that still owns the staging), and each
+// slot's pairs hold at least in_bytes and out_bytes.
+static int host_stage(hfv_ctx *ctx, size_t in_bytes, size_t out_bytes)
 {
     for (int i = 0; i < 2; ++i) {
         if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
-        if (!ctx->brh_dio[i]) {
-            HIP_TRY(hipMalloc((void **)&ctx->brh_dio[i], kBrChunk * 12));
-            HIP_TRY(hipHostMalloc((void **)&ctx->brh_hio[i], kBrChunk * 12, hipHostMallocDefault));
-        }
+        HIP_TRY(hipStreamSynchronize(ctx->hstream[i]));
     }
-    if (ctx->brh_win_cap < window) {
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipStreamSynchronize(ctx->hstream[i]));
-            if (ctx->brh_dwin[i]) (void)hipFree(ctx->brh_dwin[i]);
-            if (ctx->brh_hwin[i]) (void)hipHostFree(ctx->brh_hwin[i]);
-            ctx->brh_dwin[i] = ctx->brh_hwin[i] = nullptr;
-            HIP_TRY(hipMalloc((void **)&ctx->brh_dwin[i], kBrChunk * window));
-            HIP_TRY(hipHostMalloc((void **)&ctx->brh_hwin[i], kBrChunk * window, hipHostMallocDefault));
-        }
-        ctx->brh_win_cap = window;
+    for (int i = 0; i < 2; ++i) {
+        int rc = ctx->stage_in[i].reserve(in_bytes);
+        if (!rc) rc = ctx->stage_out[i].reserve(out_bytes);
+        if (rc) return rc;
     }
+    return 0;
+}
+
+static int wait_slot(hfv_ctx *ctx, int sl)
+{
+    HIP_TRY(hipStreamSynchronize(ctx->hstream[sl]));
+    return 0;
+}
+
+// The slot and window of a call over frames in their slots; window 0 is the default, min(slot, 256).
+static int check_slot_window(size_t slot, size_t *window)
+{
+    if (slot < 64 || (slot & 7) || slot > 65535 * 8) return fail(-EINVAL, "slot must be >= 64 and a multiple of 8");
+    if (*window == 0) *window = slot < 256 ? slot : 256;
+    if (*window < 64 || (*window & 7) || *window > slot) return fail(-EINVAL, "window must be a multiple of 8 in [64, slot]");
     return 0;
 }
 
@@ -322,22 +247,22 @@ static int brh_chunk(hfv_ctx *ctx, int sl, uint8_t *frames, size_t fstride, size
                      const uint16_t *len, const uint32_t *ifx, size_t cnt)
 {
     hipStream_t st = ctx->hstream[sl];
-    uint8_t *hio = ctx->brh_hio[sl], *dio = ctx->brh_dio[sl];
-    memcpy(hio, len, cnt * 2);
-    memcpy(hio + kBrChunk * 2, ifx, cnt * 4);
-    HIP_TRY(hipMemcpyAsync(dio, hio, kBrChunk * 6, hipMemcpyHostToDevice, st));
+    const StagePair &win = ctx->stage_in[sl], &io = ctx->stage_out[sl];
+    memcpy(io.host, len, cnt * 2);
+    memcpy(io.host + kBrChunk * 2, ifx, cnt * 4);
+    HIP_TRY(hipMemcpyAsync(io.dev, io.host, kBrChunk * 6, hipMemcpyHostToDevice, st));
     // the header windows, packed by host threads into pinned staging, then one linear DMA
-    copy_rows(ctx->brh_hwin[sl], window, frames, fstride, window, cnt);
-    HIP_TRY(hipMemcpyAsync(ctx->brh_dwin[sl], ctx->brh_hwin[sl], cnt * window, hipMemcpyHostToDevice, st));
+    copy_rows(win.host, window, frames, fstride, window, cnt);
+    HIP_TRY(hipMemcpyAsync(win.dev, win.host, cnt * window, hipMemcpyHostToDevice, st));
     int rc = with_tables(ctx, st, "br_process launch", [&](DevState *ds) {
-        return launch_br_process(br_geom(ctx), ds, ctx->brh_dwin[sl], window, (uint32_t)maxlen, (uint32_t)window,
-                                 (const uint16_t *)dio, (const uint32_t *)(dio + kBrChunk * 2), cnt,
-                                 dio + kBrChunk * 6, dio + kBrChunk * 7, (int32_t *)(dio + kBrChunk * 8),
+        return launch_br_process(br_geom(ctx), ds, win.dev, window, (uint32_t)maxlen, (uint32_t)window,
+                                 (const uint16_t *)io.dev, (const uint32_t *)(io.dev + kBrChunk * 2), cnt,
+                                 io.dev + kBrChunk * 6, io.dev + kBrChunk * 7, (int32_t *)(io.dev + kBrChunk * 8),
                                  ctx->brh_dstats, st);
     });
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->brh_hwin[sl], ctx->brh_dwin[sl], cnt * window, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(hio + kBrChunk * 6, dio + kBrChunk * 6, kBrChunk * 6, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(win.host, win.dev, cnt * window, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(io.host + kBrChunk * 6, io.dev + kBrChunk * 6, kBrChunk * 6, hipMemcpyDeviceToHost, st));
     return 0;
 }
 
@@ -346,8 +271,8 @@ static int brh_chunk(hfv_ctx *ctx, int sl, uint8_t *frames, size_t fstride, size
 static void brh_results(hfv_ctx *ctx, int sl, uint8_t *frames, size_t fstride, size_t window, size_t cnt,
                         uint8_t *action, uint8_t *verdict, int32_t *egress)
 {
-    copy_rows(frames, fstride, ctx->brh_hwin[sl], window, window, cnt);
-    const uint8_t *hio = ctx->brh_hio[sl];
+    copy_rows(frames, fstride, ctx->stage_in[sl].host, window, window, cnt);
+    const uint8_t *hio = ctx->stage_out[sl].host;
     memcpy(action, hio + kBrChunk * 6, cnt);
     memcpy(verdict, hio + kBrChunk * 7, cnt);
     memcpy(egress, hio + kBrChunk * 8, cnt * 4);
@@ -363,6 +288,61 @@ uint8_t *host_dev_ptr(hfv_ctx *ctx, const void *p, size_t bytes)
     return nullptr;
 }
 
+// The zero-copy calls' device scratch holds at least `bytes`; after a failure it is null, its size 0.
+static int zc_scratch(hfv_ctx *ctx, size_t bytes)
+{
+    if (ctx->zc_cap >= bytes) return 0;
+    if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
+    ctx->zc_meta = nullptr;
+    ctx->zc_cap = 0;
+    HIP_TRY(hipMalloc((void **)&ctx->zc_meta, bytes));
+    ctx->zc_cap = bytes;
+    return 0;
+}
+
+// The per-item arrays of one zero-copy call on stream st.  in / out give an array's device address:
+// the array itself where it lies in a registered buffer, else its offset in the scratch (grown to
+// `need` bytes when the first such array turns up), copied up at once for an input and copied back
+// by copy_back for an output.  A null array stays null.  rc holds the first failure.
+namespace {
+struct ZcArrays {
+    hfv_ctx *ctx;
+    hipStream_t st;
+    size_t need;
+    int rc = 0;
+    struct Back {
+        void *host;
+        const uint8_t *dev;
+        size_t bytes;
+    } back[3] = {};
+    int nback = 0;
+
+    uint8_t *place(const void *host, size_t bytes, size_t off, bool input)
+    {
+        if (!host || rc) return nullptr;
+        if (uint8_t *d = host_dev_ptr(ctx, host, bytes)) return d;
+        if ((rc = zc_scratch(ctx, need))) return nullptr;
+        uint8_t *d = ctx->zc_meta + off;
+        if (!input) {
+            back[nback++] = {(void *)host, d, bytes};
+        } else if (hipError_t e = hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st)) {
+            rc = hip_fail(e, "hipMemcpyAsync of a zero-copy input");
+        }
+        return d;
+    }
+    template <class T>
+    const T *in(const T *host, size_t bytes, size_t off) { return (const T *)place(host, bytes, off, true); }
+    template <class T>
+    T *out(T *host, size_t bytes, size_t off) { return (T *)place(host, bytes, off, false); }
+    int copy_back()
+    {
+        for (int k = 0; k < nback; ++k)
+            HIP_TRY(hipMemcpyAsync(back[k].host, back[k].dev, back[k].bytes, hipMemcpyDeviceToHost, st));
+        return 0;
+    }
+};
+}  // namespace
+
 // Zero-copy: the frames are in a registered (mapped) ring, so the kernel reads each header
 // window across PCIe itself and writes back only the rewritten rows; no DMA of frame bytes and
 // no retry pass (the whole frame stays addressable).  Per-frame metadata uses the caller's
@@ -373,32 +353,19 @@ static int br_zero_copy(hfv_ctx *ctx, uint8_t *dframes, size_t slot, const uint1
     hipStream_t st = ctx->stream;
     int rc = brh_stats_buffer(ctx, st);
     if (rc) return rc;
-    uint16_t *dlen = (uint16_t *)host_dev_ptr(ctx, len, n * 2);
-    uint32_t *difx = (uint32_t *)host_dev_ptr(ctx, ifx, n * 4);
-    uint8_t *dact = host_dev_ptr(ctx, action, n), *dver = host_dev_ptr(ctx, verdict, n);
-    int32_t *degr = (int32_t *)host_dev_ptr(ctx, egress, n * 4);
-    size_t need = n * 16;
-    if ((!dlen || !difx || !dact || !dver || !degr) && ctx->zc_cap < need) {
-        if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
-        ctx->zc_meta = nullptr;
-        HIP_TRY(hipMalloc((void **)&ctx->zc_meta, need));
-        ctx->zc_cap = need;
-    }
-    uint8_t *m = ctx->zc_meta;
-    if (!dlen) { dlen = (uint16_t *)m; HIP_TRY(hipMemcpyAsync(dlen, len, n * 2, hipMemcpyHostToDevice, st)); }
-    if (!difx) { difx = (uint32_t *)(m + n * 4); HIP_TRY(hipMemcpyAsync(difx, ifx, n * 4, hipMemcpyHostToDevice, st)); }
-    bool cp_act = !dact, cp_ver = !dver, cp_egr = !degr;
-    if (cp_act) dact = m + n * 2;
-    if (cp_ver) dver = m + n * 3;
-    if (cp_egr) degr = (int32_t *)(m + n * 8);
+    ZcArrays z{ctx, st, n * 16};
+    const uint16_t *dlen = z.in(len, n * 2, 0);
+    const uint32_t *difx = z.in(ifx, n * 4, n * 4);
+    uint8_t *dact = z.out(action, n, n * 2);
+    uint8_t *dver = z.out(verdict, n, n * 3);
+    int32_t *degr = z.out(egress, n * 4, n * 8);
+    if (z.rc) return z.rc;
     rc = with_tables(ctx, st, "br_process launch", [&](DevState *ds) {
         return launch_br_process(br_geom(ctx), ds, dframes, slot, (uint32_t)slot, (uint32_t)slot, dlen, difx, n, dact,
                                  dver, degr, ctx->brh_dstats, st);
     });
+    if (!rc) rc = z.copy_back();
     if (rc) return rc;
-    if (cp_act) HIP_TRY(hipMemcpyAsync(action, dact, n, hipMemcpyDeviceToHost, st));
-    if (cp_ver) HIP_TRY(hipMemcpyAsync(verdict, dver, n, hipMemcpyDeviceToHost, st));
-    if (cp_egr) HIP_TRY(hipMemcpyAsync(egress, degr, n * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return brh_add_stats(ctx, stats);
 }
@@ -424,6 +391,10 @@ int hfv::br_dev_launch(hfv_ctx *ctx, void *stream, uint8_t *dframes, size_t slot
 
 extern "C" {
 
+// Windowed host path.  Per chunk of br_chunk() frames, on alternating streams: the windows packed
+// into pinned staging, H2D of the windows + metadata, the kernel (stride = window, lengths clamped
+// to the caller's slot), D2H of the rewritten windows + results.  Then frames marked
+// HFV_BR_ACTION_RETRY (headers beyond the window) go through again with whole slots.
 int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16_t *len,
                         const uint32_t *ingress_ifindex, size_t n, size_t window, uint8_t *action,
                         uint8_t *verdict, int32_t *egress_ifindex, uint64_t *stats)
@@ -431,50 +402,43 @@ int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16
     if (n == 0) return ctx ? 0 : fail(-EINVAL, "ctx is NULL");
     if (!ctx) return fail(-EINVAL, "ctx is NULL");
     if (!frames || !len || !ingress_ifindex || !action || !verdict || !egress_ifindex) return fail(-EINVAL, "null buffer");
-    if (slot < 64 || (slot & 7) || slot > 65535 * 8) return fail(-EINVAL, "slot must be >= 64 and a multiple of 8");
-    if (window == 0) window = slot < 256 ? slot : 256;
-    if (window < 64 || (window & 7) || window > slot) return fail(-EINVAL, "window must be a multiple of 8 in [64, slot]");
+    int rc = check_slot_window(slot, &window);
+    if (rc) return rc;
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
     hc_reset();
     uint8_t *dframes = host_dev_ptr(ctx, frames, n * slot);
     if (dframes) return br_zero_copy(ctx, dframes, slot, len, ingress_ifindex, n, action, verdict, egress_ifindex, stats);
-    int rc = brh_buffers(ctx, window > slot ? slot : window);
+    rc = host_stage(ctx, kBrChunk * window, kBrChunk * 12);
     if (!rc) rc = brh_stats_buffer(ctx, ctx->hstream[0]);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->hstream[0]));
-    const size_t chunk = br_chunk(), nchunks = (n + chunk - 1) / chunk;
-    hc_add(kHcChunks, nchunks);
-    size_t first_of[2] = {0, 0}, cnt_of[2] = {0, 0};
-    for (size_t c = 0; c < nchunks + 2; ++c) {
-        int sl = (int)(c & 1);
-        if (c >= 2) {
-            HIP_TRY(hipStreamSynchronize(ctx->hstream[sl]));
-            size_t f = first_of[sl], fcnt = cnt_of[sl];
-            if (HFV_MUT_HOSTCHUNK == 4) {
-                f = first_of[sl ^ 1];
-                if (fcnt > n - f) fcnt = n - f;
+    const size_t chunk = br_chunk();
+    hc_add(kHcChunks, (n + chunk - 1) / chunk);
+    uint64_t reuses = 0;
+    rc = two_slot_chunks(
+        n, chunk, [&](int sl) { return wait_slot(ctx, sl); },
+        [&](int sl, size_t first, size_t cnt) -> int {
+            if (HFV_MUT_HOSTCHUNK == 5 && first) {
+                HIP_TRY(hipStreamSynchronize(ctx->hstream[sl ^ 1]));
+                HIP_TRY(hipMemsetAsync(ctx->brh_dstats, 0, kBrStatWords * 8, ctx->hstream[sl]));
             }
-            brh_results(ctx, sl, frames + f * slot, slot, window, fcnt, action + f, verdict + f, egress_ifindex + f);
-        }
-        if (c >= nchunks) continue;
-        if (c >= 2) hc_add(kHcReuses, 1);
-        size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
-        if (HFV_MUT_HOSTCHUNK == 5 && c >= 1) {
-            HIP_TRY(hipStreamSynchronize(ctx->hstream[sl ^ 1]));
-            HIP_TRY(hipMemsetAsync(ctx->brh_dstats, 0, kBrStatWords * 8, ctx->hstream[sl]));
-        }
-        rc = brh_chunk(ctx, sl, frames + first * slot, slot, slot, window, len + first, ingress_ifindex + first, cnt);
-        if (rc) return rc;
-        first_of[sl] = first;
-        cnt_of[sl] = cnt;
-    }
+            return brh_chunk(ctx, sl, frames + first * slot, slot, slot, window, len + first, ingress_ifindex + first, cnt);
+        },
+        [&](int sl, size_t first, size_t cnt) {
+            brh_results(ctx, sl, frames + first * slot, slot, window, cnt, action + first, verdict + first,
+                        egress_ifindex + first);
+            return 0;
+        },
+        &reuses);
+    hc_add(kHcReuses, reuses);
+    if (rc) return rc;
     // frames whose headers did not fit the window: whole slots, in rounds, through a bounce buffer
     size_t nretry = 0;
     for (size_t i = 0; i < n; ++i) nretry += action[i] == HFV_BR_ACTION_RETRY;
     hc_add(kHcRetried, nretry);
     if (nretry) {
-        rc = brh_buffers(ctx, slot);
+        rc = host_stage(ctx, kBrChunk * slot, kBrChunk * 12);
         if (rc) return rc;
         uint8_t *bounce = nullptr;
         size_t cap = nretry < chunk ? nretry : chunk;
@@ -482,7 +446,8 @@ int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16
         HIP_TRY(hipHostMalloc((void **)&bounce, cap * slot + cap * 4 + cap * 2, hipHostMallocDefault));
         uint32_t *bif = (uint32_t *)(bounce + cap * slot);
         uint16_t *blen = (uint16_t *)(bounce + cap * slot + cap * 4);
-        size_t *idx = (size_t *)malloc(cap * sizeof(size_t));
+        std::vector<size_t> idx(cap);   // where each frame of a round came from
+        const uint8_t *hwin = ctx->stage_in[0].host, *hio = ctx->stage_out[0].host;
         size_t i = 0;
         while (rc == 0 && i < n) {
             size_t cnt = 0;
@@ -501,13 +466,12 @@ int hfv_br_process_host(hfv_ctx *ctx, uint8_t *frames, size_t slot, const uint16
             if (rc == 0 && hipStreamSynchronize(ctx->hstream[0]) != hipSuccess) rc = fail(-EIO, "retry chunk");
             for (size_t k = 0; rc == 0 && k < cnt; ++k) {
                 size_t j = idx[HFV_MUT_HOSTCHUNK == 6 ? cnt - 1 - k : k];
-                memcpy(frames + j * slot, ctx->brh_hwin[0] + k * slot, slot);
-                action[j] = ctx->brh_hio[0][kBrChunk * 6 + k];
-                verdict[j] = ctx->brh_hio[0][kBrChunk * 7 + k];
-                memcpy(&egress_ifindex[j], ctx->brh_hio[0] + kBrChunk * 8 + 4 * k, 4);
+                memcpy(frames + j * slot, hwin + k * slot, slot);
+                action[j] = hio[kBrChunk * 6 + k];
+                verdict[j] = hio[kBrChunk * 7 + k];
+                memcpy(&egress_ifindex[j], hio + kBrChunk * 8 + 4 * k, 4);
             }
         }
-        free(idx);
         (void)hipHostFree(bounce);
         if (rc) return rc;
     }
@@ -551,28 +515,22 @@ int hfv_host_unregister(hfv_ctx *ctx, void *ptr)
 static int verify_records_zero_copy(hfv_ctx *ctx, const uint8_t *drecs, size_t stride, size_t n, uint64_t *pass_bits)
 {
     hipStream_t st = ctx->stream;
-    const size_t words = (n + 63) / 64;
-    uint64_t *dbits = (uint64_t *)host_dev_ptr(ctx, pass_bits, words * 8);
-    if (!dbits) {
-        if (ctx->zc_cap < words * 8) {
-            if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
-            ctx->zc_meta = nullptr;
-            ctx->zc_cap = 0;
-            HIP_TRY(hipMalloc((void **)&ctx->zc_meta, words * 8));
-            ctx->zc_cap = words * 8;
-        }
-        dbits = (uint64_t *)ctx->zc_meta;
-    }
+    ZcArrays z{ctx, st, (n + 63) / 64 * 8};
+    uint64_t *dbits = z.out(pass_bits, z.need, 0);
+    if (z.rc) return z.rc;
     const bool reader = launch_reads_tables(ctx->keysel);
     int rc = with_tables(ctx, st, "verify_records launch (zero-copy)", reader, [&](DevState *ds) {
         return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, drecs, stride, n,
                                      ctx->inf_off, ctx->hf_off, dbits, st, nullptr, nullptr, /*interleaved=*/true);
     });
+    if (!rc) rc = z.copy_back();
     if (rc) return rc;
-    if (dbits == (uint64_t *)ctx->zc_meta) HIP_TRY(hipMemcpyAsync(pass_bits, dbits, words * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
+
+// Bitmap words a chunk of cnt records copies back.
+static size_t rec_words(size_t cnt) { return HFV_MUT_HOSTCHUNK == 2 ? cnt / 64 : (cnt + 63) / 64; }
 
 // Host batch: chunks of records go host -> pinned -> device, verified, bitmap back; two
 // streams alternate so chunk k's copy-in overlaps chunk k-1's kernel and copy-out.  Records
@@ -592,56 +550,35 @@ int hfv_verify_records_host(hfv_ctx *ctx, const void *recs, size_t stride, size_
     // kHostRec bytes per record (INF at 0, HF at 8: the 20 bytes the verifier reads), so
     // PCIe moves 24 B instead of the record stride; the gather is split over host threads
     // and chunk c's gather overlaps chunk c-1's copy, kernel and copy-back on the other stream.
-    if (ctx->host_chunk < kRecChunk * kHostRec) {
-        for (int i = 0; i < 2; ++i) {
-            if (ctx->h_pin[i]) (void)hipHostFree(ctx->h_pin[i]);
-            if (ctx->d_rec[i]) (void)hipFree(ctx->d_rec[i]);
-            if (ctx->h_bits[i]) (void)hipHostFree(ctx->h_bits[i]);
-            if (ctx->d_bits[i]) (void)hipFree(ctx->d_bits[i]);
-            ctx->h_pin[i] = ctx->d_rec[i] = nullptr;
-            ctx->h_bits[i] = ctx->d_bits[i] = nullptr;
-            if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
-            HIP_TRY(hipHostMalloc((void **)&ctx->h_pin[i], kRecChunk * kHostRec, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&ctx->d_rec[i], kRecChunk * kHostRec));
-            HIP_TRY(hipHostMalloc((void **)&ctx->h_bits[i], kRecChunk / 8, hipHostMallocDefault));
-            HIP_TRY(hipMalloc((void **)&ctx->d_bits[i], kRecChunk / 8));
-        }
-        ctx->host_chunk = kRecChunk * kHostRec;
-    }
+    rc = host_stage(ctx, kRecChunk * kHostRec, kRecChunk / 8);
+    if (rc) return rc;
     const size_t chunk = rec_chunk();   // records per chunk
-    size_t nchunks = (n + chunk - 1) / chunk;
-    hc_add(kHcChunks, nchunks);
-    size_t pending_words[2] = {0, 0};
-    size_t pending_first[2] = {0, 0};
-    for (size_t c = 0; c < nchunks + 2; ++c) {
-        int slot = (int)(c & 1);
-        hipStream_t st = ctx->hstream[slot];
-        if (c >= 2) {   // retire chunk c-2 (same slot)
-            HIP_TRY(hipStreamSynchronize(st));
-            size_t to = pending_first[slot], words = pending_words[slot];
-            if (HFV_MUT_HOSTCHUNK == 1) {
-                to = pending_first[slot ^ 1];
-                if (words > (n + 63) / 64 - to) words = (n + 63) / 64 - to;
-            }
-            memcpy(pass_bits + to, ctx->h_bits[slot], words * 8);
-        }
-        if (c >= nchunks) continue;
-        if (c >= 2) hc_add(kHcReuses, 1);
-        size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
-        const size_t from = HFV_MUT_HOSTCHUNK == 3 ? first * kHostRec : first * stride;
-        gather_hf(ctx->h_pin[slot], (const uint8_t *)recs + from, stride, ctx->inf_off, ctx->hf_off, cnt);
-        HIP_TRY(hipMemcpyAsync(ctx->d_rec[slot], ctx->h_pin[slot], cnt * kHostRec, hipMemcpyHostToDevice, st));
-        rc = with_tables(ctx, st, "verify_records launch", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
-            return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, ctx->d_rec[slot],
-                                         kHostRec, cnt, 0, 8, ctx->d_bits[slot], st);
-        });
-        if (rc) return rc;
-        size_t words = HFV_MUT_HOSTCHUNK == 2 ? cnt / 64 : (cnt + 63) / 64;
-        HIP_TRY(hipMemcpyAsync(ctx->h_bits[slot], ctx->d_bits[slot], words * 8, hipMemcpyDeviceToHost, st));
-        pending_words[slot] = words;
-        pending_first[slot] = first / 64;
-    }
-    return 0;
+    hc_add(kHcChunks, (n + chunk - 1) / chunk);
+    const bool reader = launch_reads_tables(ctx->keysel);
+    uint64_t reuses = 0;
+    rc = two_slot_chunks(
+        n, chunk, [&](int sl) { return wait_slot(ctx, sl); },
+        [&](int sl, size_t first, size_t cnt) -> int {
+            hipStream_t st = ctx->hstream[sl];
+            const StagePair &in = ctx->stage_in[sl], &out = ctx->stage_out[sl];
+            const size_t from = HFV_MUT_HOSTCHUNK == 3 ? first * kHostRec : first * stride;
+            gather_hf(in.host, (const uint8_t *)recs + from, stride, ctx->inf_off, ctx->hf_off, cnt);
+            HIP_TRY(hipMemcpyAsync(in.dev, in.host, cnt * kHostRec, hipMemcpyHostToDevice, st));
+            int rc = with_tables(ctx, st, "verify_records launch", reader, [&](DevState *ds) {
+                return launch_verify_records(batch_geom(ctx), &ds->keys, &ctx->host_img->keys, ctx->keysel, in.dev,
+                                             kHostRec, cnt, 0, 8, (uint64_t *)out.dev, st);
+            });
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(out.host, out.dev, rec_words(cnt) * 8, hipMemcpyDeviceToHost, st));
+            return 0;
+        },
+        [&](int sl, size_t first, size_t cnt) {
+            memcpy(pass_bits + first / 64, ctx->stage_out[sl].host, rec_words(cnt) * 8);
+            return 0;
+        },
+        &reuses);
+    hc_add(kHcReuses, reuses);
+    return rc;
 }
 
 }  // extern "C"
@@ -691,57 +628,36 @@ static FhLayout fh_layout(size_t cnt, size_t pitch, bool with_ifx, bool with_sta
     return l;
 }
 
-static int fh_buffers(hfv_ctx *ctx, size_t pitch)
+// The staging for rows of `pitch` bytes: a full chunk with every optional part.
+static int fh_stage(hfv_ctx *ctx, size_t pitch)
 {
-    for (int i = 0; i < 2; ++i) {
-        if (!ctx->hstream[i]) HIP_TRY(hipStreamCreateWithFlags(&ctx->hstream[i], hipStreamNonBlocking));
-        if (!ctx->fh_dout[i]) {
-            const size_t out = fh_layout(kFhChunk, 0, false, true).out;
-            HIP_TRY(hipMalloc((void **)&ctx->fh_dout[i], out));
-            HIP_TRY(hipHostMalloc((void **)&ctx->fh_hout[i], out, hipHostMallocDefault));
-        }
-    }
-    if (ctx->fh_win_cap < pitch) {
-        const size_t in = fh_layout(kFhChunk, pitch, true, false).in;
-        for (int i = 0; i < 2; ++i) {
-            HIP_TRY(hipStreamSynchronize(ctx->hstream[i]));
-            if (ctx->fh_din[i]) (void)hipFree(ctx->fh_din[i]);
-            if (ctx->fh_hin[i]) (void)hipHostFree(ctx->fh_hin[i]);
-            ctx->fh_din[i] = ctx->fh_hin[i] = nullptr;
-            ctx->fh_win_cap = 0;
-            HIP_TRY(hipMalloc((void **)&ctx->fh_din[i], in));
-            HIP_TRY(hipHostMalloc((void **)&ctx->fh_hin[i], in, hipHostMallocDefault));
-        }
-        ctx->fh_win_cap = pitch;
-    }
-    return 0;
+    return host_stage(ctx, fh_layout(kFhChunk, pitch, true, false).in, fh_layout(kFhChunk, 0, false, true).out);
 }
 
-// The launch of one chunk whose parts are on the device as `l` says: the windowed kernel over
-// packed windows (it also writes the chunk's retry words: all zero where window == slot), or, for
-// the second run's whole slots, the full-slot kernel of hfv_verify_frames_fused.
-static int fh_launch(hfv_ctx *ctx, int sl, const FhLayout &l, size_t slot, size_t window, bool whole, bool with_ifx,
-                     bool with_status, size_t cnt)
+// One chunk whose parts lie in slot sl's pinned staging as `l` says: the copy up, the launch, the
+// copy back.  The launch is the windowed kernel over packed windows (it also writes the chunk's
+// retry words: all zero where window == slot), or, for the second run's whole slots, the full-slot
+// kernel of hfv_verify_frames_fused.
+static int fh_run(hfv_ctx *ctx, int sl, const FhLayout &l, size_t slot, size_t window, bool whole, bool with_ifx,
+                  bool with_status, size_t cnt)
 {
     hipStream_t st = ctx->hstream[sl];
-    uint8_t *din = ctx->fh_din[sl], *dout = ctx->fh_dout[sl];
-    return with_tables(ctx, st, "verify_frames_host launch", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
+    const StagePair &in = ctx->stage_in[sl], &out = ctx->stage_out[sl];
+    HIP_TRY(hipMemcpyAsync(in.dev, in.host, l.in, hipMemcpyHostToDevice, st));
+    int rc = with_tables(ctx, st, "verify_frames_host launch", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
         FusedWinArgs a;
         memset(&a, 0, sizeof a);
-        a.f.frames = din + l.rows;
-        a.f.slot = slot;
-        a.f.lens = (const uint16_t *)din;
-        a.f.ifindex = with_ifx ? (const uint32_t *)(din + l.ifx) : nullptr;
-        a.f.n = cnt;
-        a.f.status = with_status ? dout + l.status : nullptr;
-        a.f.bits = (unsigned long long *)dout;
-        a.f.tab = &ds->keys;
-        a.f.set = ctx->rx_set;
+        a.f = fused_args(ctx, ds, in.dev + l.rows, slot, (const uint16_t *)in.dev,
+                         with_ifx ? (const uint32_t *)(in.dev + l.ifx) : nullptr, cnt,
+                         with_status ? out.dev + l.status : nullptr, (uint64_t *)out.dev);
         if (whole) return launch_verify_frames(batch_geom(ctx), ctx->keysel, a.f, &ctx->host_img->keys, st);
         a.window = (uint32_t)window;
-        a.retry = (unsigned long long *)(dout + l.words * 8);
+        a.retry = (unsigned long long *)(out.dev + l.words * 8);
         return launch_verify_frames_win(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, st);
     });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(out.host, out.dev, l.out, hipMemcpyDeviceToHost, st));
+    return 0;
 }
 
 // Zero-copy: the frames lie in a registered (mapped) ring, so the full-slot kernel reads them in
@@ -752,47 +668,19 @@ static int verify_frames_zero_copy(hfv_ctx *ctx, const uint8_t *dframes, size_t 
 {
     hipStream_t st = ctx->stream;
     const size_t words = (n + 63) / 64;
-    const uint16_t *dlen = (const uint16_t *)host_dev_ptr(ctx, len, n * 2);
-    const uint32_t *difx = ifx ? (const uint32_t *)host_dev_ptr(ctx, ifx, n * 4) : nullptr;
-    uint8_t *dstatus = status ? host_dev_ptr(ctx, status, n) : nullptr;
-    uint64_t *dbits = (uint64_t *)host_dev_ptr(ctx, pass_bits, words * 8);
-    const size_t o_ifx = words * 8, o_len = o_ifx + n * 4, o_status = o_len + n * 2, need = o_status + n;
-    if ((!dlen || (ifx && !difx) || (status && !dstatus) || !dbits) && ctx->zc_cap < need) {
-        if (ctx->zc_meta) (void)hipFree(ctx->zc_meta);
-        ctx->zc_meta = nullptr;
-        ctx->zc_cap = 0;
-        HIP_TRY(hipMalloc((void **)&ctx->zc_meta, need));
-        ctx->zc_cap = need;
-    }
-    uint8_t *m = ctx->zc_meta;
-    const bool cp_bits = !dbits, cp_status = status && !dstatus;
-    if (!dlen) {
-        HIP_TRY(hipMemcpyAsync(m + o_len, len, n * 2, hipMemcpyHostToDevice, st));
-        dlen = (const uint16_t *)(m + o_len);
-    }
-    if (ifx && !difx) {
-        HIP_TRY(hipMemcpyAsync(m + o_ifx, ifx, n * 4, hipMemcpyHostToDevice, st));
-        difx = (const uint32_t *)(m + o_ifx);
-    }
-    if (cp_bits) dbits = (uint64_t *)m;
-    if (cp_status) dstatus = m + o_status;
+    const size_t o_ifx = words * 8, o_len = o_ifx + n * 4, o_status = o_len + n * 2;
+    ZcArrays z{ctx, st, o_status + n};
+    const uint16_t *dlen = z.in(len, n * 2, o_len);
+    const uint32_t *difx = z.in(ifx, n * 4, o_ifx);
+    uint64_t *dbits = z.out(pass_bits, words * 8, 0);
+    uint8_t *dstatus = z.out(status, n, o_status);
+    if (z.rc) return z.rc;
     int rc = with_tables(ctx, st, "verify_frames_host launch (zero-copy)", launch_reads_tables(ctx->keysel), [&](DevState *ds) {
-        FusedArgs a;
-        memset(&a, 0, sizeof a);
-        a.frames = dframes;
-        a.slot = slot;
-        a.lens = dlen;
-        a.ifindex = difx;
-        a.n = n;
-        a.status = dstatus;
-        a.bits = (unsigned long long *)dbits;
-        a.tab = &ds->keys;
-        a.set = ctx->rx_set;
+        const FusedArgs a = fused_args(ctx, ds, dframes, slot, dlen, difx, n, dstatus, dbits);
         return launch_verify_frames(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, st);
     });
+    if (!rc) rc = z.copy_back();
     if (rc) return rc;
-    if (cp_bits) HIP_TRY(hipMemcpyAsync(pass_bits, dbits, words * 8, hipMemcpyDeviceToHost, st));
-    if (cp_status) HIP_TRY(hipMemcpyAsync(status, dstatus, n, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return 0;
 }
@@ -804,82 +692,79 @@ extern "C" int hfv_verify_frames_host(hfv_ctx *ctx, const uint8_t *frames, size_
     if (!ctx) return fail(-EINVAL, "ctx is NULL");
     if (n == 0) return 0;
     if (!frames || !len || !pass_bits) return fail(-EINVAL, "null buffer");
-    if (slot < 64 || (slot & 7) || slot > 65535 * 8) return fail(-EINVAL, "slot must be >= 64 and a multiple of 8");
-    if (window == 0) window = slot < 256 ? slot : 256;
-    if (window < 64 || (window & 7) || window > slot) return fail(-EINVAL, "window must be a multiple of 8 in [64, slot]");
+    int rc = check_slot_window(slot, &window);
+    if (rc) return rc;
     if ((uintptr_t)pass_bits & 7) return fail(-EINVAL, "bitmap must be 8-byte aligned");
     DeviceGuard g(ctx->device);
     SVC_QUIESCE(ctx);
+    hc_reset();
     if (retried) *retried = 0;
     if (const uint8_t *dframes = host_dev_ptr(ctx, frames, n * slot))
         return verify_frames_zero_copy(ctx, dframes, slot, len, ingress_ifindex, n, status, pass_bits);
-    int rc = fh_buffers(ctx, window);
+    rc = fh_stage(ctx, window);
     if (rc) return rc;
     const bool with_ifx = ingress_ifindex != nullptr, with_status = status != nullptr;
-    const size_t chunk = fh_chunk(), nchunks = (n + chunk - 1) / chunk;
+    const size_t chunk = fh_chunk();
+    hc_add(kHcChunks, (n + chunk - 1) / chunk);
     // Chunk c is packed by the host threads while chunk c - 1's copy and kernel run on the other
     // stream; chunk c - 2 (same stream, same buffers) is retired first.
     std::vector<size_t> again;   // the frames to run again, in order
-    size_t first_of[2] = {0, 0}, cnt_of[2] = {0, 0};
-    for (size_t c = 0; c < nchunks + 2; ++c) {
-        const int sl = (int)(c & 1);
-        hipStream_t st = ctx->hstream[sl];
-        if (c >= 2) {
-            HIP_TRY(hipStreamSynchronize(st));
-            const size_t f = first_of[sl], cnt = cnt_of[sl];
+    uint64_t reuses = 0;
+    rc = two_slot_chunks(
+        n, chunk, [&](int sl) { return wait_slot(ctx, sl); },
+        [&](int sl, size_t first, size_t cnt) {
             const FhLayout l = fh_layout(cnt, window, with_ifx, with_status);
-            const uint64_t *w = (const uint64_t *)ctx->fh_hout[sl];
-            memcpy(pass_bits + f / 64, w, l.words * 8);
-            if (with_status) memcpy(status + f, ctx->fh_hout[sl] + l.status, cnt);
+            uint8_t *hin = ctx->stage_in[sl].host;
+            memcpy(hin, len + first, cnt * 2);
+            if (with_ifx) memcpy(hin + l.ifx, ingress_ifindex + first, cnt * 4);
+            copy_rows(hin + l.rows, window, frames + first * slot, slot, window, cnt);
+            return fh_run(ctx, sl, l, slot, window, /*whole=*/false, with_ifx, with_status, cnt);
+        },
+        [&](int sl, size_t first, size_t cnt) -> int {
+            const FhLayout l = fh_layout(cnt, window, with_ifx, with_status);
+            const uint8_t *hout = ctx->stage_out[sl].host;
+            const uint64_t *w = (const uint64_t *)hout;
+            memcpy(pass_bits + first / 64, w, l.words * 8);
+            if (with_status) memcpy(status + first, hout + l.status, cnt);
             for (size_t k = 0; k < l.words; ++k) {
                 uint64_t r = w[l.words + k];
                 const size_t left = cnt - k * 64;
                 if (left < 64 && (r >> left)) return fail(-EIO, "retry word %zu marks frames past the chunk's %zu", k, cnt);
-                for (; r; r &= r - 1) again.push_back(f + k * 64 + (size_t)__builtin_ctzll(r));
+                for (; r; r &= r - 1) again.push_back(first + k * 64 + (size_t)__builtin_ctzll(r));
             }
-        }
-        if (c >= nchunks) continue;
-        const size_t first = c * chunk, cnt = n - first < chunk ? n - first : chunk;
-        const FhLayout l = fh_layout(cnt, window, with_ifx, with_status);
-        uint8_t *hin = ctx->fh_hin[sl];
-        memcpy(hin, len + first, cnt * 2);
-        if (with_ifx) memcpy(hin + l.ifx, ingress_ifindex + first, cnt * 4);
-        copy_rows(hin + l.rows, window, frames + first * slot, slot, window, cnt);
-        HIP_TRY(hipMemcpyAsync(ctx->fh_din[sl], hin, l.in, hipMemcpyHostToDevice, st));
-        rc = fh_launch(ctx, sl, l, slot, window, /*whole=*/false, with_ifx, with_status, cnt);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->fh_hout[sl], ctx->fh_dout[sl], l.out, hipMemcpyDeviceToHost, st));
-        first_of[sl] = first;
-        cnt_of[sl] = cnt;
-    }
+            return 0;
+        },
+        &reuses);
+    hc_add(kHcReuses, reuses);
+    if (rc) return rc;
+    hc_add(kHcRetried, again.size());
     if (retried) *retried = again.size();
     if (again.empty()) return 0;
     // The second run: the marked frames' whole slots, gathered into the pinned staging chunk by
     // chunk, through the full-slot kernel; each verdict into the frame's own bit, each status into
     // its own byte.
-    rc = fh_buffers(ctx, slot);
+    rc = fh_stage(ctx, slot);
     if (rc) return rc;
     for (size_t done = 0; done < again.size(); done += chunk) {
         const size_t cnt = again.size() - done < chunk ? again.size() - done : chunk;
         const size_t *idx = again.data() + done;
         const FhLayout l = fh_layout(cnt, slot, with_ifx, with_status);
-        uint8_t *hin = ctx->fh_hin[0];
+        uint8_t *hin = ctx->stage_in[0].host;
         uint16_t *blen = (uint16_t *)hin;
         uint32_t *bifx = (uint32_t *)(hin + l.ifx);
         for (size_t k = 0; k < cnt; ++k) {
             blen[k] = len[idx[k]];
             if (with_ifx) bifx[k] = ingress_ifindex[idx[k]];
         }
-        parallel_rows(cnt, [=](size_t a, size_t b) {
+        host_rows(cnt, [=](size_t a, size_t b) {
             for (size_t k = a; k < b; ++k) memcpy(hin + l.rows + k * slot, frames + idx[k] * slot, slot);
         });
-        hipStream_t st = ctx->hstream[0];
-        HIP_TRY(hipMemcpyAsync(ctx->fh_din[0], hin, l.in, hipMemcpyHostToDevice, st));
-        rc = fh_launch(ctx, 0, l, slot, slot, /*whole=*/true, with_ifx, with_status, cnt);
+        hc_add(kHcRounds, 1);
+        rc = fh_run(ctx, 0, l, slot, slot, /*whole=*/true, with_ifx, with_status, cnt);
+        if (!rc) rc = wait_slot(ctx, 0);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->fh_hout[0], ctx->fh_dout[0], l.out, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        const uint64_t *w = (const uint64_t *)ctx->fh_hout[0];
+        const uint8_t *hout = ctx->stage_out[0].host;
+        const uint64_t *w = (const uint64_t *)hout;
         for (size_t k = 0; k < cnt; ++k) {
             const size_t j = HFV_MUT_HOSTWIN == 2 ? k : idx[k];
             const uint64_t bit = (uint64_t)1 << (j & 63);
@@ -887,7 +772,7 @@ extern "C" int hfv_verify_frames_host(hfv_ctx *ctx, const uint8_t *frames, size_
                 pass_bits[j / 64] |= bit;
             else
                 pass_bits[j / 64] &= ~bit;
-            if (with_status) status[j] = ctx->fh_hout[0][l.status + k];
+            if (with_status) status[j] = hout[l.status + k];
         }
     }
     return 0;

@@ -14,7 +14,10 @@ The tests that set the chunk size or cap the grid use test hooks and run in a ch
 lib/libscionhfv_test.so (conftest.rerun_on_test_build).
 
 `make hostwin` builds three libraries with one wrong step each (csrc/hfv_frames_fused_kernel.hip); this
-module must fail on every one: run it with HFV_LIB=lib/libscionhfv_hostwinN.so HFV_TEST_BUILD_CHILD=1."""
+module must fail on every one: run it with HFV_LIB=lib/libscionhfv_hostwinN.so HFV_TEST_BUILD_CHILD=1.
+The call runs on the two-slot schedule of csrc/hfv_host_pipe.h, so on lib/libscionhfv_hostchunk1.so
+(`make hostchunk`: a retired chunk's results go to the other slot's place) both cases of
+test_chunks_of_128 must fail as well, by an assertion or the call's own -EIO, never by a fault."""
 import ctypes
 import errno
 
@@ -24,6 +27,7 @@ import pytest
 import br_topo as T
 import frames_hostmem as H
 import frames_rx_ref as R
+import host_chunks as HC
 import orc
 import scion_hfv as hfv
 from conftest import rerun_on_test_build
@@ -234,10 +238,17 @@ def test_chunks_of_128(request, ctx, n):
     ctx.set_internal_ifindices(iset1())
     try:
         hfv.Ctx.debug_frames_host_chunk(128)
+        def counts_hold(retried):
+            got = hfv.Ctx.debug_host_chunk_counts()
+            model = HC.counts(n, 128)
+            assert (got[0], got[3]) == (model[0], model[3]) and got[2] == retried, ("counts", got, model, retried)
+
         for window in (64, 128, 256):
             _, _, retried = check(ctx, frames, lens, n, ifidx, window, what="chunk 128")
+            counts_hold(retried)
             assert window != 64 or retried > 128              # two bounce chunks or more
-        check(ctx, frames, lens, n, None, 128, what="chunk 128, no status", status=False)
+        _, _, retried = check(ctx, frames, lens, n, None, 128, what="chunk 128, no status", status=False)
+        counts_hold(retried)
     finally:
         hfv.Ctx.debug_frames_host_chunk(0)
     assert hfv.lib().hfv_debug_frames_host_chunk(ctypes.c_size_t(100)) == -errno.EINVAL   # not a multiple of 64

@@ -12,22 +12,24 @@ compared unchanged afterwards.  Integer work: every comparison is exact.
 Every test uses test hooks and runs in a child process on lib/libscionhfv_test.so
 (conftest.rerun_on_test_build), and restores the hooks in a `finally`.
 
-`make hostchunk` builds six libraries with one wrong step each (csrc/hfv_host_path.cpp); this module must
-fail on every one, by assertions alone: run it with HFV_LIB=lib/libscionhfv_hostchunkN.so
-HFV_TEST_BUILD_CHILD=1.  What fails (of the 13 cases; every failure is an assertion):
-  hostchunk1  a retired bitmap to the other slot's place: the 9 record cases (test_records_*, both
-              test_records_every_chunk_edge, test_three_host_threads,
-              test_records_router_records_on_one_ctx): word 0 keeps its pre-fill
-  hostchunk2  a ragged chunk's floor(cnt / 64) words: the same but test_records_chunk_sizes_back_to_back
-              (6656 records: no ragged chunk); first at n = 63, whose only word keeps its pre-fill
+`make hostchunk` builds five libraries with one wrong step each (csrc/hfv_host_path.cpp; number 1 in the
+schedule itself, csrc/hfv_host_pipe.h); this module must fail on every one, by assertions alone: run it
+with HFV_LIB=lib/libscionhfv_hostchunkN.so HFV_TEST_BUILD_CHILD=1.  What fails (of the 13 cases; every
+failure is an assertion):
+  hostchunk1  a retired chunk's results to the place of the chunk on the other slot: all 13.  The 9
+              record cases (test_records_*, both test_records_every_chunk_edge, test_three_host_threads,
+              test_records_router_records_on_one_ctx): word 0 keeps its pre-fill.  The 6 router cases
+              (both test_router_every_row, test_router_window_grows_and_shrinks, test_router_ipv6_tables,
+              test_three_host_threads, test_records_router_records_on_one_ctx): from two chunks on,
+              frames keep their pre-fill or carry another chunk's results.  (The router's copy of this
+              step was hostchunk4 while the two paths had a loop each; that number is retired.)
+  hostchunk2  a ragged chunk's floor(cnt / 64) words: the 9 record cases but
+              test_records_chunk_sizes_back_to_back (6656 records: no ragged chunk); first at n = 63,
+              whose only word keeps its pre-fill
   hostchunk3  later chunks gathered at first * 24: the same 9; the second chunk's words are those of
               other records (the compact layout, stride 24, cannot tell: the wider ones fail)
-  hostchunk4  a retired chunk's results at the other slot's first frame: the 6 router cases (both
-              test_router_every_row, test_router_window_grows_and_shrinks, test_router_ipv6_tables,
-              test_three_host_threads, test_records_router_records_on_one_ctx): from two chunks on,
-              frames keep their pre-fill or carry another chunk's results
-  hostchunk5  the counters zeroed before every chunk: the same 6, by the counters alone (every frame
-              result is right), from the first row with a retry round on
+  hostchunk5  the counters zeroed before every chunk: the 6 router cases, by the counters alone (every
+              frame result is right), from the first row with a retry round on
   hostchunk6  a retry round scattered backwards: the same 6; the retried frames carry each other's
               results (one retried frame, n = 1, cannot tell)"""
 import contextlib

@@ -3,10 +3,18 @@ become vacuous: the restated schedule on cases worked out by hand, the asserted 
 model, every retried count against the parser's rule (window 64) and against "hop field past byte
 256" (window 256), the placement against the oracle router on the whole frames (and the reference
 program where it is built), the conditions on the record corpora, and the test hooks' exports and
-argument checks."""
+argument checks.
+
+The schedule and the host worker pool themselves (csrc/hfv_host_pipe.h, free of HIP) run here too:
+tests/host_pipe_driver.cpp, built under the thread sanitizer and under the address and undefined-
+behaviour sanitizers, prints what two_slot_chunks calls, which must be what the model says."""
 import ctypes
 import errno
+import os
+import re
 import subprocess
+
+import pytest
 
 import numpy as np
 
@@ -16,6 +24,7 @@ import hf_bits as HB
 import host_chunks as HC
 import orc
 import scion_hfv as hfv
+from conftest import ROOT
 
 HOOKS = ("hfv_debug_records_host_chunk", "hfv_debug_br_host_chunk", "hfv_debug_host_inline_rows",
          "hfv_debug_host_chunk_counts")
@@ -219,3 +228,96 @@ def test_hook_arguments():
         L.hfv_debug_records_host_chunk(sz(0))
         L.hfv_debug_br_host_chunk(sz(0))
         L.hfv_debug_host_inline_rows(sz(0))
+
+
+# ---- the real schedule and the real pool, as a host program under the sanitizers ---------------
+
+BY_HAND = ((1, 128), (128, 128), (385, 128), (229, 64), (677, 100), (129, 128), (256, 128), (257, 128), (677, 128))
+PAIRS = BY_HAND + tuple((n, chunk) for n in (1, 63, 64, 65, 128, 129, 385, 677) for chunk in (64, 100, 128))
+
+
+@pytest.fixture(scope="module", params=["thread", "address,undefined"])
+def pipe_driver(request, tmp_path_factory):
+    """tests/host_pipe_driver.cpp over csrc/hfv_host_pipe.h, built with -fsanitize=<param>; run(*args)
+    runs it (nothing preloaded) and returns its output lines.  A sanitizer report fails the run."""
+    exe = str(tmp_path_factory.mktemp("host_pipe") / "host_pipe_driver")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-pthread", "-Wall", "-Wextra", "-Werror",
+           "-fsanitize=" + request.param, "-fno-sanitize-recover=undefined",
+           "-I" + os.path.join(ROOT, "scion-xdp-br_amd", "csrc"), "-o", exe,
+           os.path.join(ROOT, "tests", "host_pipe_driver.cpp")]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and re.search(r"sanitize|[atu]b?san", b.stderr):
+        pytest.skip("sanitizer runtime unavailable: " + b.stderr[-300:])
+    assert b.returncode == 0, b.stderr[-3000:]
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=1:exitcode=66", ASAN_OPTIONS="detect_leaks=1:abort_on_error=1",
+               UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+
+    def run(*args):
+        r = subprocess.run([exe] + [str(a) for a in args], env=env, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0 and "Sanitizer" not in r.stderr, (args, r.returncode, r.stdout[-2000:], r.stderr[-4000:])
+        return r.stdout.splitlines()
+    return run
+
+
+def _cases(lines):
+    """{(n, chunk): ([(call, slot, first, count) | ("wait", slot)], rc, reuses)} of the driver's output."""
+    out, key = {}, None
+    for line in lines:
+        w = line.split()
+        if w[0] == "case":
+            key = (int(w[1]), int(w[2]))
+            out[key] = [[], None, None]
+        elif w[0] == "end":
+            out[key][1:] = int(w[1]), int(w[2])
+        else:
+            out[key][0].append((w[0],) + tuple(int(x) for x in w[1:]))
+    return out
+
+
+def _model_calls(n, chunk, upto=None):
+    """What two_slot_chunks must call, by HC.events and HC.schedule (upto: stop after that launch)."""
+    sched = HC.schedule(n, chunk)
+    out = []
+    for kind, c in HC.events(n, chunk):
+        _, slot, first, cnt, _ = sched[c]
+        if kind == "retire":
+            out.append(("wait", slot))
+        out.append((kind, slot, first, cnt))
+        if kind == "launch" and c == upto:
+            break
+    return out
+
+
+def test_driver_runs_the_model_schedule(pipe_driver):
+    assert len(set(PAIRS)) == 8 * 3 + 3                                # the grid and by-hand's three outside it
+    got = _cases(pipe_driver("sched", *[x for pair in dict.fromkeys(PAIRS) for x in pair]))
+    assert set(got) == set(PAIRS)
+    for (n, chunk), (calls, rc, reuses) in got.items():
+        assert calls == _model_calls(n, chunk), (n, chunk)
+        assert rc == 0 and reuses == HC.slot_reuses(n, chunk) == HC.counts(n, chunk)[3], (n, chunk)
+        assert [c[2] // chunk for c in calls if c[0] == "retire"] == HC.retire_order(n, chunk)
+        assert [c[1:] for c in calls if c[0] == "launch"] == [s[1:4] for s in HC.schedule(n, chunk)]
+
+
+def test_driver_stops_at_the_first_error(pipe_driver):
+    """submit fails on chunk 2 of 7: the driver returns its code and calls nothing more: chunks 1 and 2
+    are neither waited for nor retired."""
+    (key, (calls, rc, reuses)), = _cases(pipe_driver("fail", 677, 100, 2, -5)).items()
+    assert key == (677, 100) and rc == -5 and reuses == 1
+    assert calls == _model_calls(677, 100, upto=2) and calls[-1] == ("launch", 0, 200, 100)
+    assert [c for c in calls if c[0] == "retire"] == [("retire", 0, 0, 100)]
+    # a failure in the last chunk leaves the two chunks in flight unretired as well
+    (_, (calls, rc, _)), = _cases(pipe_driver("fail", 385, 128, 3, 7)).items()
+    assert rc == 7 and calls == _model_calls(385, 128, upto=3)
+
+
+def test_pool_touches_every_row_once(pipe_driver):
+    """1, 3 and 8 threads, 0, 1, 7, 8 and 4097 rows, through parallel_rows (inline and through the pool)
+    and HostPool::run: every row once, by counters that are not atomic."""
+    assert pipe_driver("pool") == ["pool ok"]
+
+
+def test_pool_back_to_back_jobs(pipe_driver):
+    """2000 jobs on one pool of 8: the generation and countdown hand-off, under the thread sanitizer
+    with no report (and under the address sanitizer)."""
+    assert pipe_driver("stress", 2000) == ["stress ok 2000"]
