@@ -47,11 +47,16 @@ extern "C" int hfv_debug_br_split(size_t frames)
     g_br_split = frames;
     return 0;
 }
+// hfv_debug_br_last_variant: the kernel the last k_br_process launch ran, 1 staged or 2 direct (0: no
+// launch yet), so a test of one variant can assert that it ran that one (tests/test_gpu_br_deal.py).
+static int g_br_variant = 0;
+extern "C" int hfv_debug_br_last_variant(void) { return g_br_variant; }
 LaunchGeom br_geom(const hfv_ctx *ctx)
 {
     LaunchGeom g = ctx->geom;
     g.br_grid_cap = g_br_grid;
     g.br_split_cap = g_br_split;
+    g.br_variant_out = &g_br_variant;
     return g;
 }
 // hfv_debug_batch_grid: blocks per k_verify_batches launch (0 = one block per CU up to the tile

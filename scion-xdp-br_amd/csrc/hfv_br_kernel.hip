@@ -47,6 +47,17 @@
 #ifndef HFV_MUT_CSUM
 #define HFV_MUT_CSUM 0
 #endif
+// HFV_MUT_BRDEAL = 1..6 (`make brdeal`): one wrong step each in the tile dealing of k_br_process (1 a
+// staged block's range ends one tile late where the ranges are ragged, 2 every claim of the staged loop
+// that draws a number of 16 mod 17 is thrown away and drawn again, 3 the direct loop steps by the grid
+// instead of the grid's waves, 4 the direct loop and 5 the detached loop end after their first round,
+// 6 both kernels let the lane at index n through: outputs at n and one count too many, the direct kernel
+// over frame n - 1 once more, the staged one over the zeros its empty buffer range returns), for the
+// libraries tests/test_gpu_br_deal.py must fail on.  Each only skips or repeats work on tiles of the call or
+// writes the output elements at n.  0 (the default, every product build): none of them.
+#ifndef HFV_MUT_BRDEAL
+#define HFV_MUT_BRDEAL 0
+#endif
 
 namespace hfv {
 
@@ -845,6 +856,9 @@ __device__ __forceinline__ uint64_t claim_tile(uint32_t lane, uint64_t tb0, uint
 {
     uint32_t g = 0;
     if (lane == 0) g = __hip_atomic_fetch_add(&s_br_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#if HFV_MUT_BRDEAL == 2   // (the first 16 draws, 0..15, are the waves' first tiles: only the loop's claims are hit)
+    if (lane == 0 && g % 17 == 16) g = __hip_atomic_fetch_add(&s_br_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+#endif
     const uint64_t t = tb0 + __builtin_amdgcn_readfirstlane(g);
     return t < tb1 ? t : ntiles;
 }
@@ -890,6 +904,7 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
                 verdict[i] = 0;
                 egress[i] = -1;
             }
+            if (HFV_MUT_BRDEAL == 5) break;
         }
         return;   // block-uniform: no barrier below is reached by only part of the block
     }
@@ -919,7 +934,8 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
         fetch_lane(lens, ifidx, n, lane, tt, pre);
     };
     // staged: this block's tiles [tb0, tb1)
-    const uint64_t tb0 = ntiles * blockIdx.x / gridDim.x, tb1 = ntiles * (blockIdx.x + 1) / gridDim.x;
+    const uint64_t tb0 = ntiles * blockIdx.x / gridDim.x,
+                   tb1 = (ntiles * (blockIdx.x + 1) + (HFV_MUT_BRDEAL == 1 ? gridDim.x - 1 : 0)) / gridDim.x;
     if constexpr (kStaged) t = claim_tile(lane, tb0, tb1, ntiles);
     uint64_t tnext = t + nwaves;
     if constexpr (kStaged) {
@@ -927,7 +943,7 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
         // (a builtin, so the waitcnt pass knows: the loop's vmcnt(kBrChunks) assumes that many younger stores)
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) expcnt(7) lgkmcnt(15)
     }
-    for (; t < ntiles; t = kStaged ? tnext : t + nwaves) {
+    for (; t < ntiles; t = kStaged ? tnext : t + (HFV_MUT_BRDEAL == 3 ? gridDim.x : nwaves)) {
         if constexpr (kStaged) {
             // the loads of this tile were issued at the end of the previous one, before its
             // write-back stores: wait for everything but those stores, then stage the rows
@@ -941,10 +957,11 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
         const uint32_t len = pre.len, ifx = pre.ifx;
         uint64_t i = t * 64 + lane;
         uint32_t dirty = 0;
-        if (i < n) {
+        if (HFV_MUT_BRDEAL == 6 ? i <= n : i < n) {
             BrFrame k = {};
-            k.p = pkts + i * slot;
-            k.po = out + i * slot;
+            const uint64_t fi = HFV_MUT_BRDEAL == 6 && i == n ? n - 1 : i;   // (the mutant's lane stays on the call's frames)
+            k.p = pkts + fi * slot;
+            k.po = out + fi * slot;
             k.win = WIN;
             k.row = (wib * 64 + lane) * kBrRow;
             k.len = (int)(len <= maxlen ? len : maxlen);
@@ -979,6 +996,7 @@ __global__ __launch_bounds__(BLOCK) void k_br_process(const DevState *__restrict
             }
             wave_sync();   // every lane is done with the rows before they are restaged
         }
+        if (HFV_MUT_BRDEAL == 4 && !kStaged) break;
     }
     if constexpr (STATS) {
         __syncthreads();
@@ -1004,6 +1022,7 @@ int launch_br_process(const LaunchGeom &g, const DevState *st, uint8_t *pkts, si
     // (the staged loop addresses a tile of 64 slots through 32-bit buffer offsets: 64 * slot < 2^31)
     bool staged = slot >= (size_t)kBrWin && slot % 16 == 0 && ((uintptr_t)pkts & 15) == 0 &&
                   ((uintptr_t)out & 15) == 0 && slot < ((size_t)1 << 25);
+    if (g.br_variant_out) *g.br_variant_out = staged ? 1 : 2;   // test build only (hfv_debug_br_last_variant)
     using K = void (*)(const DevState *, const uint8_t *, uint8_t *, uint64_t, uint32_t, uint32_t,
                        const uint16_t *,
                        const uint32_t *, uint64_t, uint8_t *, uint8_t *, int32_t *, unsigned long long *);

@@ -174,6 +174,9 @@ struct LaunchGeom {
     // always 0 in the product library): blocks per k_br_process launch, frames per split launch
     unsigned br_grid_cap = 0;
     uint64_t br_split_cap = 0;
+    // where launch_br_process notes the kernel it chose, 1 staged or 2 direct (the test build's
+    // hfv_debug_br_last_variant; null in the product library)
+    int *br_variant_out = nullptr;
     // the same for the batch-list launch (hfv_debug_batch_grid): blocks per k_verify_batches launch
     unsigned batch_grid_cap = 0;
     // and for the macinput, tag, verdict-counter and generator launches (hfv_debug_aux_grid): blocks

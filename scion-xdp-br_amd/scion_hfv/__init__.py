@@ -22,7 +22,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv.so")
 # the test build: the same library plus the test hooks (hfv_debug_relay_delay, _publish_delay,
-# _br_grid, _br_split, _batch_grid, _aux_grid, _loop_host_stage, _service_set_weights, the host paths' chunk hooks);
+# _br_grid, _br_split, _br_last_variant, _batch_grid, _aux_grid, _loop_host_stage, _service_set_weights, the host paths' chunk hooks);
 # loaded only by tests (HFV_LIB),
 # never by the product path
 TEST_LIB_PATH = os.path.join(PKG_ROOT, "lib", "libscionhfv_test.so")
@@ -674,6 +674,11 @@ class Ctx:
     def debug_br_grid(blocks):
         """Test-only: cap k_br_process launches at `blocks` blocks (0 = default geometry)."""
         _check(lib().hfv_debug_br_grid(ctypes.c_uint(blocks)))
+
+    @staticmethod
+    def debug_br_last_variant():
+        """Test-only: the kernel the last k_br_process launch ran: "staged", "direct" or None."""
+        return {1: "staged", 2: "direct"}.get(lib().hfv_debug_br_last_variant())
 
     @staticmethod
     def debug_batch_grid(blocks):

@@ -41,7 +41,7 @@ def test_lib_exports_every_declared_symbol():
 
 
 TEST_HOOKS = ("hfv_debug_loop_host_stage", "hfv_debug_publish_delay", "hfv_debug_relay_delay", "hfv_debug_br_grid",
-              "hfv_debug_br_split", "hfv_debug_batch_grid", "hfv_debug_aux_grid", "hfv_debug_service_set_weights",
+              "hfv_debug_br_split", "hfv_debug_br_last_variant", "hfv_debug_batch_grid", "hfv_debug_aux_grid", "hfv_debug_service_set_weights",
               "hfv_debug_records_host_chunk", "hfv_debug_br_host_chunk", "hfv_debug_host_inline_rows",
               "hfv_debug_host_chunk_counts")
 
