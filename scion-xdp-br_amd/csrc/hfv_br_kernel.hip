@@ -58,6 +58,17 @@
 #ifndef HFV_MUT_BRDEAL
 #define HFV_MUT_BRDEAL 0
 #endif
+// HFV_MUT_PATHWALK = 1..9 (`make pathwalk`): one wrong step each in the SCION path walk (1 seg_end taken as
+// the true end of the current segment, 2 CurrINF stored as min(curr_inf, 3), 3 CurrHF stored without
+// & 0x3f, 4 keep_mac_bytes left out, so the MAC check reads after the rewrite, 5 mac_b8 substituting at
+// INF+4..5, 6 seg_id1 read whenever INF + 16 fits, 7 the next_hf >= num_hf test placed after the switch,
+// 8 num_inf taken as the index of the last non-zero SegLen plus one; 9 is the same num_inf in frame_locate,
+// hfv_frame_parse.h, for the frame kernels), for the libraries tests/test_gpu_br_walk.py must fail on.
+// Each reads and writes only bytes of its own frame that the product reads or writes on some frame.
+// 0 (the default, every product build): none of them.
+#ifndef HFV_MUT_PATHWALK
+#define HFV_MUT_PATHWALK 0
+#endif
 
 namespace hfv {
 
@@ -321,6 +332,7 @@ __device__ __forceinline__ int parse_scion_path(BrFrame &k, int off)
     k.seg0 = (k.h_meta >> 12) & 0x3fu;
     uint32_t seg1 = (k.h_meta >> 6) & 0x3fu, seg2 = k.h_meta & 0x3fu;
     k.num_inf = (k.seg0 > 0) + (seg1 > 0) + (seg2 > 0);
+    if (HFV_MUT_PATHWALK == 8) k.num_inf = seg2 ? 3u : seg1 ? 2u : k.seg0 ? 1u : 0u;
     k.num_hf = k.seg0 + seg1 + seg2;
     k.curr_inf = (k.h_meta >> 30) & 0x03u;
     k.curr_hf = (k.h_meta >> 24) & 0x3fu;
@@ -332,6 +344,8 @@ __device__ __forceinline__ int parse_scion_path(BrFrame &k, int off)
         inf += 8;
         if (beyond(k, inf + 8)) return -1;
         k.seg_id1 = rd16(k, inf + 2);
+    } else if (HFV_MUT_PATHWALK == 6 && inf + 16 <= k.lim) {
+        k.seg_id1 = rd16(k, inf + 10);
     }
     k.hf = off + (int)k.num_inf * 8 + (int)k.curr_hf * 12;
     if (beyond(k, k.hf + 12)) return -1;
@@ -384,10 +398,10 @@ __device__ __forceinline__ bool as_ingress(BrFrame &k)
     defer_verify(k, k.inf, k.hf, sw16(beta));
     if (!c) k.seg_id0 = sw16(beta);
     uint32_t seg_end = k.seg0;   // path_processing.h:84-86 adds seg0 for every index
-    if (k.curr_inf >= 1) seg_end += k.seg0;
-    if (k.curr_inf >= 2) seg_end += k.seg0;
+    if (k.curr_inf >= 1) seg_end += HFV_MUT_PATHWALK == 1 ? (k.h_meta >> 6) & 0x3fu : k.seg0;
+    if (k.curr_inf >= 2) seg_end += HFV_MUT_PATHWALK == 1 ? k.h_meta & 0x3fu : k.seg0;
     uint32_t next_hf = k.curr_hf + 1;
-    if (next_hf >= k.num_hf) {
+    if (HFV_MUT_PATHWALK != 7 && next_hf >= k.num_hf) {
         k.verdict = V_NOT_IMPLEMENTED;
         return false;
     }
@@ -400,6 +414,10 @@ __device__ __forceinline__ bool as_ingress(BrFrame &k)
             k.verdict = V_PARSE_ERROR;
             return false;
         }
+    }
+    if (HFV_MUT_PATHWALK == 7 && next_hf >= k.num_hf) {
+        k.verdict = V_NOT_IMPLEMENTED;
+        return false;
     }
     return true;
 }
@@ -631,7 +649,8 @@ __device__ __forceinline__ void rewrite(BrFrame &k)
     udp_res += (uint64_t)nd_port;
     udp_res += (uint64_t)ns_port;
     // path_type is SCION here (the only type process_packet lets through)
-    uint32_t meta = (k.h_meta & 0x00ffffffu) | ((k.curr_hf & 0x3fu) << 24) | (k.curr_inf << 30);
+    uint32_t meta = (k.h_meta & 0x00ffffffu) | ((k.curr_hf & (HFV_MUT_PATHWALK == 3 ? 0xffu : 0x3fu)) << 24) |
+                    ((HFV_MUT_PATHWALK == 2 && k.curr_inf > 3u ? 3u : k.curr_inf) << 30);
     wr32(k, k.meta, sw32(meta));
     udp_res += (uint64_t)sw32(meta);
     int inf = k.inf;
@@ -653,7 +672,10 @@ __device__ __forceinline__ void rewrite(BrFrame &k)
 // segment switch, INF+10.  With CurrINF past the info fields (parse_scion_path does not bound
 // it) either can fall inside the hop field whose MAC is checked; the BPF code read that
 // macinput before the rewrite (path_processing.h:39-57), so the bytes it would have seen are
-// kept here and substituted at the check (mac_b8).
+// kept here and substituted at the check (mac_b8).  Over seg0 0..63, num_inf 0..3, CurrINF 0..3 and
+// CurrHF 0..63 only the store at INF+2 can do so on a frame that reaches the check, at INF - HF in
+// {0, 4, 8}: the store at INF+10 needs a segment switch, a switch needs CurrHF + 1 = seg0 * k, and then
+// INF+10 lies before or behind the hop field (tests/br_walk.py enumerates it).  `clob & 2` is defensive only.
 __device__ __forceinline__ void keep_mac_bytes(BrFrame &k)
 {
     const int a = k.inf + 2, b = k.inf + 10, lo = k.mac_hf + 1, hi = k.mac_hf + 11;   // hop-field bytes read
@@ -664,7 +686,8 @@ __device__ __forceinline__ void keep_mac_bytes(BrFrame &k)
 
 __device__ __forceinline__ uint32_t mac_b8(const BrFrame &k, int off)
 {
-    if ((k.clob & 1u) && (off == k.inf + 2 || off == k.inf + 3)) return (k.orig_ab >> (8 * (off - k.inf - 2))) & 0xffu;
+    constexpr int a = HFV_MUT_PATHWALK == 5 ? 4 : 2;   // (mutant 5: two bytes too far)
+    if ((k.clob & 1u) && (off == k.inf + a || off == k.inf + a + 1)) return (k.orig_ab >> (8 * (off - k.inf - a))) & 0xffu;
     if ((k.clob & 2u) && (off == k.inf + 10 || off == k.inf + 11))
         return (k.orig_ab >> (16 + 8 * (off - k.inf - 10))) & 0xffu;
     return rd8(k, off);
@@ -726,7 +749,7 @@ __device__ __forceinline__ int process_packet(BrFrame &k)
     k.nh = ext ? 1u : sib ? 2u : 0u;
     k.fwd = f;
     k.sib_if = fwd.sib_iface;
-    if (k.need_mac) keep_mac_bytes(k);
+    if (k.need_mac && HFV_MUT_PATHWALK != 4) keep_mac_bytes(k);
     rewrite(k);
     k.egress_ifindex = egress;
     return -1;

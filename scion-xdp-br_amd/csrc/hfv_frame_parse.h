@@ -30,6 +30,12 @@
 #define HFV_HD inline
 #endif
 
+// HFV_MUT_PATHWALK = 9 (`make pathwalk`, listed in hfv_br_kernel.hip): num_inf taken as the index of the
+// last non-zero SegLen plus one, in the frame kernels' builds only.  0 (the default): the reference's count.
+#ifndef HFV_MUT_PATHWALK
+#define HFV_MUT_PATHWALK 0
+#endif
+
 namespace hfv {
 
 enum : int {
@@ -102,7 +108,7 @@ HFV_HD FrameLoc frame_locate(const R &r, int end)
     if (off > end) return frame_bound_stop(loc);
     const uint32_t h_meta = __builtin_bswap32(r.u32(meta));
     const uint32_t seg0 = (h_meta >> 12) & 0x3fu, seg1 = (h_meta >> 6) & 0x3fu, seg2 = h_meta & 0x3fu;
-    const uint32_t num_inf = (seg0 > 0) + (seg1 > 0) + (seg2 > 0);
+    const uint32_t num_inf = HFV_MUT_PATHWALK == 9 ? (seg2 ? 3u : seg1 ? 2u : seg0 ? 1u : 0u) : (seg0 > 0) + (seg1 > 0) + (seg2 > 0);
     const uint32_t curr_inf = (h_meta >> 30) & 0x03u, curr_hf = (h_meta >> 24) & 0x3fu;
     int inf = off + (int)curr_inf * 8;
     loc.inf = (uint32_t)inf;
