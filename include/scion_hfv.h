@@ -310,6 +310,54 @@ int hfv_verify_frames_batches(hfv_ctx *ctx, const struct hfv_frame_batch *batche
  * -EINVAL. */
 int hfv_verify_frames_batches_timed(hfv_ctx *ctx, const struct hfv_frame_batch *batches, size_t count,
                                     void *stream, float *kernel_ms);
+/* Frames addressed by DESCRIPTORS into one buffer, verified in place in ONE launch on `stream`:
+ * hfv_verify_frames_fused for a caller whose frames lie where the NIC put them -- an AF_XDP UMEM
+ * (an RX ring hands out struct xdp_desc entries: chunk offset plus headroom, in whatever order the
+ * fill ring recycled the chunks) or a DPDK mempool -- with no gather into slots first. */
+#define HFV_FRAME_DESC_MAX_LEN 65535u
+#define HFV_FRAME_BAD_DESC 255        /* status of a frame whose descriptor is rejected; no router verdict has this value */
+struct hfv_frame_desc {               /* 16 bytes; the layout of AF_XDP's struct xdp_desc */
+    uint64_t addr;                    /* byte offset of the frame's first byte inside the buffer */
+    uint32_t len;                     /* frame length in bytes */
+    uint32_t ifindex;                 /* receiving interface (xdp_desc's `options` word, filled by the caller) */
+};
+/* The validity rule, on the host (the kernel applies the same function per frame): 1 iff
+ * len <= HFV_FRAME_DESC_MAX_LEN and addr <= umem_bytes and len <= umem_bytes - addr, else 0.  No
+ * sum is formed, so nothing wraps at 2^64; len == 0 is valid (and reads nothing). */
+int hfv_frame_desc_ok(uint64_t addr, uint32_t len, size_t umem_bytes);
+/* umem, desc, status (nullable: not written) and pass_bits are device pointers.  Frame i is the
+ * bytes [umem + desc[i].addr, umem + desc[i].addr + desc[i].len) when desc[i] is valid
+ * (hfv_frame_desc_ok); descriptors may come in any order, may overlap and may repeat a frame; addr
+ * and umem need no alignment (a umem that is not 16-byte aligned, or shorter than 128 bytes, takes
+ * the kernel without 16-byte staging loads, with the same results).
+ * Equivalence: take any slot that is a multiple of 8, at least 64 and at least every valid len,
+ * copy each valid frame to frames + i*slot with len[i] = desc[i].len and ingress_ifindex[i] =
+ * desc[i].ifindex: pass_bits[0 .. (n+63)/64) and status[0..n) are bit-identical to what
+ * hfv_verify_frames_fused writes for that copy under the same key table, keysel and
+ * internal-ifindex set, except at the indices of invalid descriptors, which get bit 0 and status
+ * HFV_FRAME_BAD_DESC.  Bits at or past n of the last word are 0; every bitmap word is written whole
+ * by one plain store, so the bitmap needs no initialisation.  Direction: a frame is internal iff
+ * its ifindex is in the ctx's set (hfv_ctx_set_internal_ifindices); an empty set makes every frame
+ * external.  The fail-closed rules are those of hfv_verify_frames_fused.
+ * What is read: no byte outside [umem, umem + umem_bytes), and none at all on behalf of an invalid
+ * descriptor; no descriptor at or past desc + n.  The outputs depend on no byte of the buffer
+ * outside the frame's own [addr, addr + len): bytes past len count as absent although real memory
+ * follows them.  umem and desc are never written; no bitmap word at or past (n+63)/64 and no
+ * status byte at or past n is touched.
+ * Stream-ordered: no allocation, no host synchronisation; like every data-path call it first stops
+ * a running verify service.  Key-table publication holds as for hfv_verify_frames_fused.
+ * Checks: NULL ctx is -EINVAL, even with n == 0; n == 0 returns 0 and touches nothing; with n > 0,
+ * -EINVAL with a message in hfv_last_error() for a NULL desc, a desc that is not 8-byte aligned, a
+ * pass_bits that is NULL or not 8-byte aligned, a NULL umem with umem_bytes > 0, or n > 2^36.
+ * The descriptors' contents live on the device: they are judged per frame, never by the return
+ * value. */
+int hfv_verify_frames_desc(hfv_ctx *ctx, const uint8_t *umem, size_t umem_bytes, const struct hfv_frame_desc *desc,
+                           size_t n, uint8_t *status, uint64_t *pass_bits, void *stream);
+/* Same, then waits and stores the kernel's execution time (dispatch start/stop) in *kernel_ms.
+ * NULL kernel_ms: -EINVAL. */
+int hfv_verify_frames_desc_timed(hfv_ctx *ctx, const uint8_t *umem, size_t umem_bytes,
+                                 const struct hfv_frame_desc *desc, size_t n, uint8_t *status, uint64_t *pass_bits,
+                                 void *stream, float *kernel_ms);
 /* One frame on the host: hfv_frame_locate, the copy of the two fields and, for from_internal != 0,
  * the normalisation above.  Returns the status; inf and hf are all zeros for a non-zero status;
  * -EINVAL for NULL arguments.  The scalar counterpart of hfv_extract_records_rx. */

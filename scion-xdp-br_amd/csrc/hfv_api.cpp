@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "hfv_ctx.h"
+#include "hfv_frame_desc.h"
 
 namespace hfv {
 
@@ -63,8 +64,9 @@ LaunchGeom br_geom(const hfv_ctx *ctx)
 // count), for every call that ends in launch_verify_batches.  With 1 to 3 blocks a list of a few
 // thousand tiles gives every wave a hundred tiles and more over many batches -- the dealing the real
 // grid reaches only at 2^24 records (tests/test_gpu_tile_deal.py).  The same cap holds for the
-// k_verify_frames launch of hfv_verify_frames_fused (tests/test_gpu_frames_fused.py) and the
-// k_verify_frames_list launches of hfv_verify_frames_batches (tests/test_gpu_frames_list.py).
+// k_verify_frames launch of hfv_verify_frames_fused (tests/test_gpu_frames_fused.py), the
+// k_verify_frames_list launches of hfv_verify_frames_batches (tests/test_gpu_frames_list.py) and the
+// k_verify_frames_desc launch of hfv_verify_frames_desc (tests/test_gpu_frames_desc.py).
 static unsigned g_batch_grid = 0;
 extern "C" int hfv_debug_batch_grid(unsigned blocks)
 {
@@ -614,6 +616,62 @@ int hfv_verify_frames_fused_timed(hfv_ctx *ctx, const uint8_t *frames, size_t sl
     if (n == 0) return 0;
     return timed(ctx, kernel_ms, [&](hipEvent_t ev0, hipEvent_t ev1) {
         return verify_frames_fused(ctx, frames, slot, len, ingress_ifindex, n, status, pass_bits, stream, ev0, ev1);
+    });
+}
+
+int hfv_frame_desc_ok(uint64_t addr, uint32_t len, size_t umem_bytes)
+{
+    return frame_desc_ok(addr, len, (uint64_t)umem_bytes) ? 1 : 0;
+}
+
+// Frames given by descriptors into one buffer, verified in place in one launch
+// (k_verify_frames_desc): the preamble of verify_frames_fused.  What the descriptors hold is on the
+// device and judged there, per frame.  ctx is not NULL and n != 0.
+static int verify_frames_desc(hfv_ctx *ctx, const uint8_t *umem, size_t umem_bytes, const struct hfv_frame_desc *desc,
+                              size_t n, uint8_t *status, uint64_t *pass_bits, void *stream, hipEvent_t ev0,
+                              hipEvent_t ev1)
+{
+    if (!desc) return fail(-EINVAL, "null descriptor array");
+    if ((uintptr_t)desc & 7) return fail(-EINVAL, "descriptors must be 8-byte aligned");
+    if (!pass_bits) return fail(-EINVAL, "null buffer");
+    if ((uintptr_t)pass_bits & 7) return fail(-EINVAL, "bitmap must be 8-byte aligned");
+    if (!umem && umem_bytes) return fail(-EINVAL, "null buffer of %zu bytes", umem_bytes);
+    if (n > ((size_t)1 << 36)) return fail(-EINVAL, "%zu frames (at most 2^36)", n);
+    DeviceGuard g(ctx->device);
+    SVC_QUIESCE(ctx);
+    const bool reader = launch_reads_tables(ctx->keysel);
+    return with_tables(ctx, (hipStream_t)stream, "verify_frames_desc launch", reader, [&](DevState *ds) {
+        DescArgs a;
+        memset(&a, 0, sizeof a);
+        a.umem = umem;
+        a.umem_bytes = umem_bytes;
+        a.desc = desc;
+        a.n = n;
+        a.status = status;
+        a.bits = (unsigned long long *)pass_bits;
+        a.tab = &ds->keys;
+        a.set = ctx->rx_set;
+        return launch_verify_frames_desc(batch_geom(ctx), ctx->keysel, a, &ctx->host_img->keys, stream, ev0, ev1);
+    });
+}
+
+int hfv_verify_frames_desc(hfv_ctx *ctx, const uint8_t *umem, size_t umem_bytes, const struct hfv_frame_desc *desc,
+                           size_t n, uint8_t *status, uint64_t *pass_bits, void *stream)
+{
+    if (!ctx) return fail(-EINVAL, "ctx is NULL");
+    if (n == 0) return 0;
+    return verify_frames_desc(ctx, umem, umem_bytes, desc, n, status, pass_bits, stream, nullptr, nullptr);
+}
+
+int hfv_verify_frames_desc_timed(hfv_ctx *ctx, const uint8_t *umem, size_t umem_bytes,
+                                 const struct hfv_frame_desc *desc, size_t n, uint8_t *status, uint64_t *pass_bits,
+                                 void *stream, float *kernel_ms)
+{
+    if (!ctx || !kernel_ms) return fail(-EINVAL, "null argument");
+    *kernel_ms = 0.0f;
+    if (n == 0) return 0;
+    return timed(ctx, kernel_ms, [&](hipEvent_t ev0, hipEvent_t ev1) {
+        return verify_frames_desc(ctx, umem, umem_bytes, desc, n, status, pass_bits, stream, ev0, ev1);
     });
 }
 

@@ -408,6 +408,27 @@ bool frames_stageable(const uint8_t *frames, size_t slot);
 int launch_verify_frames_list(const LaunchGeom &g, int keysel, bool staged, const FusedListArgs &a, void *stream,
                               void *ev_start = nullptr, void *ev_stop = nullptr);
 
+// Frames given by descriptors into one buffer (hfv_frames_desc_kernel.hip, hfv_verify_frames_desc,
+// k_verify_frames_desc): the one by-value kernel argument.  The caller fills everything above key0;
+// the launcher fills the slot-0 key rows (key_prologue).  An empty set: every frame is external.
+// tab is read under KEYSEL_IFID only.
+struct DescArgs {
+    const uint8_t *umem;
+    uint64_t umem_bytes;
+    const hfv_frame_desc *desc;
+    uint64_t n;
+    uint8_t *status;               // nullable
+    unsigned long long *bits;
+    const DevKeyTable *tab;
+    RxSet set;
+    uint32_t key0[kDevKeyRows * 4];
+    uint32_t key0_ok;
+};
+// The grid of launch_verify_frames; the staged kernel where umem is 16-byte aligned and holds a
+// whole 128-byte window, the kernel that reads every byte from global memory otherwise.
+int launch_verify_frames_desc(const LaunchGeom &g, int keysel, DescArgs a, const DevKeyTable *host_keys, void *stream,
+                              void *ev_start = nullptr, void *ev_stop = nullptr);
+
 // pinned key map (hfv_keymap.cpp)
 int keymap_open_ro(const char *path, const void **mapping);
 int keymap_create(const char *path, uint32_t mode);   // empty map (header only) if the file does not exist

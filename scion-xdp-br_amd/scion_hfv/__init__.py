@@ -42,6 +42,8 @@ FRAME_PARSE_ERROR = 17
 FRAME_NOT_SCION = 26
 FRAME_NOT_IMPLEMENTED = 34
 FRAME_REC_STRIDE = 24  # compact record: set_record_layout(0, 8), InfoField | HopField | 4 B pad
+FRAME_DESC_MAX_LEN = 65535  # hfv_verify_frames_desc: the longest frame a descriptor may name
+FRAME_BAD_DESC = 255        # ... and the status of a frame whose descriptor is rejected
 
 
 class HfvError(RuntimeError):
@@ -95,6 +97,9 @@ def lib():
         "hfv_verify_frames_fused_timed": (i32, [vp, vp, sz, vp, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]),
         "hfv_verify_frames_batches": (i32, [vp, vp, sz, vp]),
         "hfv_verify_frames_batches_timed": (i32, [vp, vp, sz, vp, ctypes.POINTER(ctypes.c_float)]),
+        "hfv_frame_desc_ok": (i32, [u64, u32, sz]),
+        "hfv_verify_frames_desc": (i32, [vp, vp, sz, vp, sz, vp, vp, vp]),
+        "hfv_verify_frames_desc_timed": (i32, [vp, vp, sz, vp, sz, vp, vp, vp, ctypes.POINTER(ctypes.c_float)]),
         "hfv_frame_extract": (i32, [vp, sz, i32, vp, vp]),
         "hfv_ctx_describe": (i32, [vp, ctypes.c_char_p, sz]),
         "hfv_ctx_attach_keymap": (i32, [vp, ctypes.c_char_p]),
@@ -280,6 +285,25 @@ class FrameBatch(ctypes.Structure):
     _fields_ = [("frames", ctypes.c_void_p), ("slot", ctypes.c_size_t), ("len", ctypes.c_void_p),
                 ("ingress_ifindex", ctypes.c_void_p), ("n", ctypes.c_size_t), ("status", ctypes.c_void_p),
                 ("pass_bits", ctypes.c_void_p)]
+
+
+class FrameDesc(ctypes.Structure):
+    """struct hfv_frame_desc (hfv_verify_frames_desc): 16 bytes, the layout of AF_XDP's struct xdp_desc
+    with the receiving ifindex in its `options` word"""
+    _fields_ = [("addr", ctypes.c_uint64), ("len", ctypes.c_uint32), ("ifindex", ctypes.c_uint32)]
+
+
+try:  # the same 16 bytes as a numpy structured dtype (None without numpy)
+    import numpy as _np
+    FRAME_DESC_DTYPE = _np.dtype([("addr", "<u8"), ("len", "<u4"), ("ifindex", "<u4")])
+except Exception:  # pragma: no cover - numpy is optional for C-style use
+    FRAME_DESC_DTYPE = None
+
+
+def frame_desc_ok(addr, len, umem_bytes):
+    """hfv_frame_desc_ok: whether hfv_verify_frames_desc follows a descriptor (addr, len) into a buffer
+    of umem_bytes bytes: len <= 65535, addr <= umem_bytes and len <= umem_bytes - addr."""
+    return bool(lib().hfv_frame_desc_ok(addr, len, umem_bytes))
 
 
 class LoopConfig(ctypes.Structure):
@@ -573,6 +597,21 @@ class Ctx:
         ms = ctypes.c_float(0.0)
         _check(lib().hfv_verify_frames_fused_timed(self._h, _ptr(frames), slot, _ptr(lens), _ptr(ingress_ifindex), n,
                                                    _ptr(status), _ptr(pass_bits), _stream(stream), ctypes.byref(ms)))
+        return ms.value
+
+    def verify_frames_desc(self, umem, umem_bytes, desc, n, pass_bits, status=None, stream=None):
+        """hfv_verify_frames_desc: frames given by descriptors (FRAME_DESC_DTYPE / FrameDesc, on the
+        device) into one device buffer, verified in place in one launch.  The bits (and status) are
+        those of verify_frames_fused on a slot copy of the frames; a rejected descriptor gives bit 0
+        and status FRAME_BAD_DESC."""
+        _check(lib().hfv_verify_frames_desc(self._h, _ptr(umem), umem_bytes, _ptr(desc), n, _ptr(status),
+                                            _ptr(pass_bits), _stream(stream)))
+
+    def verify_frames_desc_timed(self, umem, umem_bytes, desc, n, pass_bits, status=None, stream=None):
+        """verify_frames_desc, waited for; returns the kernel's execution time in ms."""
+        ms = ctypes.c_float(0.0)
+        _check(lib().hfv_verify_frames_desc_timed(self._h, _ptr(umem), umem_bytes, _ptr(desc), n, _ptr(status),
+                                                  _ptr(pass_bits), _stream(stream), ctypes.byref(ms)))
         return ms.value
 
     @staticmethod
